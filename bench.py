@@ -11,7 +11,9 @@ A step = ROUNDS_PER_STEP simulation rounds (Shadow scheduling windows). A packet
 one send_packet call past the DNS check (sent or loss-dropped) or one packet event popped
 at its destination. value = all ranks' packet events / max-rank wall time.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]; a plain
+run sets up, warms up, times the K steps and prints the result line; --full adds the CPU
+baselines and the parity checks (main's --help). For N > 1 under
 torch.distributed.run (one rank per GPU, hosts sharded, RCCL exchange inside libsgn).
 Scaling is STRONG by default: the workload's hosts (C: 100k) are sharded over the N GPUs,
 as BASELINE.json names config C ("100k synthetic hosts ... sharded over 8 GPUs");
@@ -215,6 +217,54 @@ def shard_check(ctx, dist, rank, world, n_hosts, rounds_done, build_unsharded):
                             "against the oracle at N=1)"}
     dist.barrier()
     return out
+
+
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: the files of all ranks together stay below this
+HASH_FIELDS = ("tx", "rx", "app", "rng")  # 64-bit hashes: no float64 holds one, so two halves
+
+
+def _f64(a, split):
+    """u64 values as float64, exactly: hashes as (high 32 bits, low 32 bits) in a trailing
+    axis of 2, counters and times (below 2^53) as they are."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if split:
+        return np.stack([a >> np.uint64(32), a & np.uint64(0xFFFFFFFF)], axis=-1).astype(np.float64)
+    assert not len(a) or int(a.max()) < 1 << 53
+    return a.astype(np.float64)
+
+
+def dump_outputs(path, ctx, n_hosts, rank, world):
+    """--dump-outputs: what a caller of the timed path (ctx.run) holds after the last timed
+    step, as DIR/<name>.npy in float64: `stats` (the counters, STAT_KEYS order), `window`
+    (start ns, end ns, active), both as high and low 32-bit halves, and per host of this
+    rank's shard `digest_<field>` (DIGEST_KEYS; the hashes tx/rx/app/rng as halves, the
+    counters as they are) with `host_ids` naming the rows. A shard whose digests would pass
+    its share of DUMP_MAX_BYTES (1 / N of it, so all ranks together stay below 64 MB) writes
+    a fixed seeded sample of its hosts. The workload is seeded and the engine bit-reproducible,
+    so two builds given the same arguments can be compared file for file. With N > 1 every
+    rank writes its shard as <name>.rank<r>.npy."""
+    d = pathlib.Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 else ""
+    lo, hi = sgn.C.c_uint32(0), sgn.C.c_uint32(n_hosts)
+    if world > 1:
+        assert sgn.load().sgn_shard_range(n_hosts, rank, world, sgn.C.byref(lo), sgn.C.byref(hi)) == 0
+    lo, hi = lo.value, hi.value
+    st = ctx.stats()
+    ws, we, act = ctx.window()
+    dg = ctx.digests(lo, hi)
+    rows = np.arange(hi - lo)
+    keep = DUMP_MAX_BYTES // world // (2 * sgn.DIGEST_DTYPE.itemsize + 8)
+    if len(rows) > keep:
+        rows = np.sort(np.random.default_rng(20240).choice(len(rows), size=keep, replace=False))
+    arrays = {"stats": _f64([st[k] for k in STAT_KEYS], True),
+              "window": _f64([ws, we, int(act)], True),
+              "host_ids": _f64(rows + lo, False)}
+    for f in DIGEST_KEYS:
+        arrays[f"digest_{f}"] = _f64(dg[f][rows], f in HASH_FIELDS)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(d / f"{name}{sfx}.npy", a)
 
 
 def cpu_baseline(g, used, hosts, cfg, tr, args, gpu):
@@ -493,7 +543,16 @@ def main():
     ap.add_argument("--rounds-per-step", type=int, default=100)
     ap.add_argument("--cpu-budget-s", type=float, default=12.0,
                     help="wall budget of the CPU mode samples after the parity run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: at N = 1 the CPU baselines and the "
+                         "parity check against the oracle; at N > 1 the other form of the APSP build and "
+                         "the unsharded re-run that checks the sharded results (a plain run sets up, warms "
+                         "up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left (counters, window, per-host "
+                         "digests) as DIR/<name>.npy; see dump_outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full at N = 1: skip the CPU baselines and the parity check")
     ap.add_argument("--codel-cap", type=int, default=None,
                     help="CoDel run slots per host on average (the shared page pool's size)")
     ap.add_argument("--one-gpu", action="store_true",
@@ -504,7 +563,7 @@ def main():
     ap.add_argument("--exchange-slot", type=int, default=None,
                     help="N > 1: per-peer exchange slot in runs (it grows when a round needs more)")
     ap.add_argument("--no-shard-check", action="store_true",
-                    help="N > 1: skip the unsharded re-run on rank 0 that checks the sharded results")
+                    help="with --full at N > 1: skip the unsharded re-run on rank 0 that checks the sharded results")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -576,7 +635,7 @@ def main():
     ctx.routes_build(g, used)         # steady state: the build time proper
     apsp = ctx.routes_timing()
     apsp_shard = None
-    if world > 1:
+    if world > 1 and args.full:
         # the other form, timed the same way (second build), bit for bit against the first
         lat_a, loss_a = ctx.routes_copy()
         other = "SGN_APSP_REPLICATED" if apsp["shards"] > 1 else "SGN_APSP_SHARDED"
@@ -749,14 +808,16 @@ def main():
     out["sim_time_reached_ms"] = (ws - sgn.SIMULATION_START) / 1e6
     out["sim_ms_per_step"] = out["sim_time_reached_ms"] / (args.steps + args.warmup)
     ok = apsp_shard is None or apsp_shard["equal_on_all_ranks"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, hosts.n, rank, world)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         gpu = {"rounds_timed": rounds, "stats": st1, "window": (ws, we, act),
                "digests": ctx.digests(0, hosts.n)}
         out["cpu_baseline"], par = cpu_baseline(g, used, hosts, cfg, tr, args, gpu)
         out["parity"] = par["ok"]
         out["parity_detail"] = par
         ok = ok and par["ok"]
-    if world > 1 and not args.no_shard_check:
+    if world > 1 and args.full and not args.no_shard_check:
         def unsharded():
             c1 = sgn.Context(device=local)
             c1.routes_build(g, used)

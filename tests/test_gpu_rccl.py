@@ -43,7 +43,7 @@ def test_rccl_two_ranks_one_gpu_match_unsharded(graph, xsz, port, workload, pool
     cmd = [sys.executable, "-u", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
            "--steps", "2", "--warmup", "1", "--one-gpu", "--hosts", "100000", "--rounds-per-step", "70",
-           "--workload", workload] + extra
+           "--workload", workload, "--full"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -75,7 +75,7 @@ def test_xpeer_two_processes_one_gpu_persistent(workload, port, launcher):
     cmd = [sys.executable, "-u", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port)] if launcher else [sys.executable, "-u"]
     cmd += ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--one-gpu", "--rounds-per-step", "70",
-            "--workload", workload]
+            "--workload", workload, "--full"]
     if workload == "D":
         cmd += ["--hosts", "100000"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
@@ -95,7 +95,7 @@ def test_xpeer_refusal_on_one_gpu_falls_back_everywhere():
     env = dict(os.environ, SGN_GRAPH="0", NCCL_DEBUG="WARN", TMPDIR="/tmp", SGN_XPEER_SHARED="1",
                SGN_XREFUSE_RANK="1")
     cmd = [sys.executable, "-u", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--one-gpu",
-           "--rounds-per-step", "40", "--hosts", "20000"]
+           "--rounds-per-step", "40", "--hosts", "20000", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -110,7 +110,8 @@ def test_rccl_eight_ranks_one_gpu_match_unsharded():
     env = dict(os.environ, NCCL_DEBUG="WARN", TMPDIR="/tmp")
     cmd = [sys.executable, "-u", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", "29546", "bench.py", "--gpus", "8",
-           "--steps", "2", "--warmup", "1", "--one-gpu", "--hosts", "100000", "--rounds-per-step", "40"]
+           "--steps", "2", "--warmup", "1", "--one-gpu", "--hosts", "100000", "--rounds-per-step", "40",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -132,7 +133,7 @@ def test_rccl_two_ranks_import_spill_hot_slabs():
     cmd = [sys.executable, "-u", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29547", "bench.py", "--gpus", "2",
            "--steps", "2", "--warmup", "1", "--one-gpu", "--workload", "H", "--hosts", "20000",
-           "--nodes", "50", "--rounds-per-step", "40"]
+           "--nodes", "50", "--rounds-per-step", "40", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
