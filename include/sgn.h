@@ -239,6 +239,68 @@ int sgn_round(sgn_ctx* ctx, uint64_t* min_next_event);
  * ends. rounds_done may be NULL. */
 int sgn_run(sgn_ctx* ctx, uint64_t max_rounds, uint64_t* rounds_done);
 
+/* ---- run-control: run to a simulated time, snapshot, rewind ----
+ * The reference fork's run-control (core/manager.rs:49-111, :1117-1442) pauses at window
+ * boundaries, runs one window (n), runs N simulated seconds (cN), and restarts (r, rN) — by
+ * re-running from t = 0, because its state is live Linux processes. Here a simulation is device
+ * buffers plus a few host counters and the engine is bit-deterministic, so a snapshot is exact:
+ *   n  = sgn_run(ctx, 1, ..)                 s  = sgn_hosts_next_event_time
+ *   cN = sgn_run_until(ctx, now + N, ..)     rN = sgn_snapshot_restore(first) + sgn_run_until(N)
+ * All of it is single-shard: a context created with shard_count > 1 or joined to a local shard
+ * group gets SGN_ESTATE (a multi-shard snapshot or pause needs a collective; not provided). */
+
+/* Runs whole windows until the next window would start at or after t_emulated (EmulatedTime,
+ * i.e. SGN_SIMULATION_START + simulated ns), or the simulation ends — the fork's rule "pause
+ * when min_next_event_time >= target" (manager.rs:1372-1382). t_emulated at or below the current
+ * window start runs nothing (rounds_done = 0). The comparison runs on the device at every round
+ * edge, so persistent launches still run many rounds each; sgn_run and sgn_round never pause.
+ * rounds_done may be NULL. */
+int sgn_run_until(sgn_ctx* ctx, uint64_t t_emulated, uint64_t* rounds_done);
+
+/* A snapshot of the simulation. Opaque; owned by the context it came from (sgn_snapshot_free, or
+ * sgn_destroy for what is left). A context may hold any number of them and restore them in any
+ * order, any number of times. */
+typedef struct sgn_snapshot sgn_snapshot;
+
+/* Saves the simulation as it is now. Valid after sgn_sim_init, between calls, at a resolved
+ * round edge: a round still held for a pool (or runs in the calendar's spill area) is resolved
+ * first, as sgn_run does on entry, and CPU-held host RNG states (sgn_rng_*) go back to the device
+ * before they are copied. It does not change the simulation: a run with a save in the middle is
+ * bit-identical to one without. The event calendar is stored packed (its live runs only), every
+ * other mutable buffer whole. SGN_ENOMEM leaves nothing behind. */
+int sgn_snapshot_save(sgn_ctx* ctx, sgn_snapshot** out);
+
+/* Puts the context back into exactly the state at the save: the device state, the host-side
+ * simulation state (rounds enqueued, submission handles and per-host submission counts, drain
+ * records held for the caller, slab extensions), the growth counters sgn_engine_info reports
+ * (codel_pool_grows, calendar_grows, calendar_spill_runs, slab_extensions, spill_area_grows,
+ * rounds_held, codel_page_allocs), and the pool layout: pools that grew after the save (slab
+ * capacity, slab extensions, CoDel pages, spill area) return to the saved sizes, so the run after
+ * a restore grows them again at the same rounds. CPU-held RNG states are dropped.
+ * NOT rewound, because they belong to the sequence of launches and not to the simulation: the
+ * persistent kernels' residency census and epochs, persistent_grid's fallback state
+ * (persistent_fallbacks), and the kernel-time samples of sgn_kernel_times (measurements).
+ * Trace records are append-only: restore sets the record count back and the re-run writes the
+ * same records again. Drain records the caller already took with sgn_drain stay the caller's;
+ * records still on the device or held at the save come back.
+ * Errors: SGN_EINVAL for a null argument or a snapshot that is not this context's; SGN_ESTATE
+ * without a simulation or for a snapshot taken before the last sgn_sim_init; SGN_ENOMEM with
+ * nothing changed. */
+int sgn_snapshot_restore(sgn_ctx* ctx, const sgn_snapshot* snap);
+
+/* Frees one snapshot (a null argument, or a snapshot that is not this context's: no effect). */
+void sgn_snapshot_free(sgn_ctx* ctx, sgn_snapshot* snap);
+
+typedef struct sgn_snapshot_info {
+  uint64_t rounds, window_start, window_end; /* the round count and window at the save */
+  uint64_t device_bytes, host_bytes;         /* what the snapshot holds */
+  uint64_t calendar_runs, calendar_bytes;    /* packed section: runs and their bytes (32 each) */
+  uint64_t calendar_pool_bytes;              /* the unpacked pool + extensions it stands for */
+  double save_ms;                            /* HIP-event time of the device part of the save */
+  double pack_ms;                            /* ... of which the calendar's scan + pack kernels */
+} sgn_snapshot_info;
+int sgn_snapshot_info_get(const sgn_snapshot* snap, sgn_snapshot_info* out);
+
 /* Whole-simulation counters (summed over owned hosts). */
 typedef struct sgn_stats {
   uint64_t rounds;

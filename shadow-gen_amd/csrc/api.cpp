@@ -58,6 +58,7 @@ void dev_free(sgn_ctx* ctx, void* p, size_t bytes) {
 
 sgn_ctx::~sgn_ctx() {
   for (sgn_stage* st : stages) st->ctx = nullptr;  // the caller still owns (and destroys) them
+  sgn::snapshots_release(this);
   sgn::free_sim(this);
   if (d_lat) hipFree(d_lat);
   if (d_loss) hipFree(d_loss);

@@ -2293,7 +2293,8 @@ __device__ void finalize_fused(const DevSim& S, uint32_t lane, uint32_t nch, uin
     st_dev(&C->active, min_next < ne ? 1u : 0u);
     if (min_next < ne) {  // the next round's guards (hold before it runs)
       const uint64_t need = codel_round_bound(S, occ, min_next, ne);
-      const uint32_t hold = (pfree < need ? HOLD_CODEL : 0u) | (spilled ? HOLD_SPILL : 0u);
+      const uint32_t hold = (pfree < need ? HOLD_CODEL : 0u) | (spilled ? HOLD_SPILL : 0u) |
+                            (min_next >= ld_dev(&C->pause_at) ? HOLD_PAUSE : 0u);  // (sgn_run_until)
       if (hold) {
         st_dev(&C->hold, hold);
         st_dev(&C->hold_need, need);
@@ -3437,6 +3438,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds(const DevSim* __restrict__ Sg,
   struct RoundLDS {
     uint64_t ws, we, pend_ws, pend_we, pend_nb1, pg_avail;
     uint64_t pg_alloc, occ, nspill, hold_need;  // CoDel pages taken, calendar runs, runs spilled
+    uint64_t pause_at;                          // Ctrl::pause_at as of the launch (sgn_run_until)
     uint32_t active, ks, pend_new, pend, ngap, hold;
   };
   __shared__ RoundLDS rs;
@@ -3453,6 +3455,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds(const DevSim* __restrict__ Sg,
     rs.nspill = ld_dev(&C->spill_n);
     rs.hold = ld_dev(&C->hold);  // (a round still held: the launch returns at once)
     rs.hold_need = ld_dev(&C->hold_need);
+    rs.pause_at = ld_dev(&C->pause_at);  // (read once: every workgroup decides alike)
   }
   // (the launch's first round number is read back at its end: nothing else writes it, and a
   // register live across the whole launch spilled the PERIODIC big-slab kernel)
@@ -3584,7 +3587,8 @@ __global__ __launch_bounds__(64, 2) void k_rounds(const DevSim* __restrict__ Sg,
       rs.nspill += e.nspill;
       if (e.active) {  // the next round's guards: every workgroup decides alike (same values)
         const uint64_t need = codel_round_bound(S, rs.occ, e.ws, e.we);
-        rs.hold = (pages_free(rs.pg_avail, rs.pg_alloc) < need ? HOLD_CODEL : 0u) | (rs.nspill ? HOLD_SPILL : 0u);
+        rs.hold = (pages_free(rs.pg_avail, rs.pg_alloc) < need ? HOLD_CODEL : 0u) | (rs.nspill ? HOLD_SPILL : 0u) |
+                  (e.ws >= rs.pause_at ? HOLD_PAUSE : 0u);
         rs.hold_need = need;
       }
       if (w == wbk) {
@@ -5137,8 +5141,11 @@ int resolve_hold(sgn_ctx* ctx) {
   // (the bound again for the layout as it is now: spilled runs may be due in the held round)
   const uint64_t need = std::max(c.hold_need, codel_need_host(ctx));
   const uint64_t free = c.pg_avail > c.pg_alloc ? c.pg_avail - c.pg_alloc : 0;
-  if (free < need && (rc = grow_codel(ctx, need - free))) return rc;
-  ctx->rounds_held++;
+  // (a pause is sgn_run_until's stop, not a pool's: it is released like one, but not counted,
+  // and alone it grows nothing — the run goes on exactly as one without the pause would)
+  if ((c.hold & ~HOLD_PAUSE) && free < need && (rc = grow_codel(ctx, need - free))) return rc;
+  if (c.hold & HOLD_PAUSE) ctx->paused = true;
+  if (c.hold & ~HOLD_PAUSE) ctx->rounds_held++;
   c.hold = 0;
   c.hold_need = 0;
   SGN_HIP(ctx, hipMemcpy((char*)ctx->S.ctrl + offsetof(Ctrl, hold), &c.hold, 4, hipMemcpyHostToDevice));
@@ -5249,6 +5256,8 @@ void time_collect(sgn_ctx* ctx) {
 int ctrl_sync(sgn_ctx* ctx) { return sync_ctrl(ctx); }
 int grow_exchange_slot(sgn_ctx* ctx) { return grow_exchange_slot_impl(ctx); }
 int resolve_pools(sgn_ctx* ctx) { return resolve_hold(ctx); }
+int sim_upload(sgn_ctx* ctx) { return upload_sim(ctx); }
+void round_kernels_resize(sgn_ctx* ctx) { size_round_kernels(ctx, ctx->S); }
 
 void drop_graph(sgn_ctx* ctx) {
   if (ctx->gexec) hipGraphExecDestroy(ctx->gexec);
@@ -6010,6 +6019,7 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
   c.keep_min = INVALID;
   c.last_min_next = INVALID;
   c.prev_we = SIM_START;
+  c.pause_at = EMU_MAX;
   c.pg_tail = c.pg_avail = S.cq_pages - nH;  // the free ring holds the pages beyond the hosts' first
   // multi-shard exchange size: RCCL rounds start at min(slot, kXszInit) runs per peer and
   // grow with the high-water mark; a local shard group copies counts, so it uses the slot
@@ -6078,6 +6088,8 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
   SGN_HIP(ctx, hipDeviceSynchronize());
   ctx->S = S;
   ctx->sim_ready = true;
+  ctx->sim_gen++;  // (snapshots of the simulation before this one are refused from here)
+  ctx->paused = false;
   ctx->rounds_enqueued = 0;
   for (int i = 0; i < K_NUM; i++) ctx->kt[i] = {kKernelNames[i], 0, 0.0, 0};
   return 0;
@@ -6121,6 +6133,9 @@ int sgn_run(sgn_ctx* ctx, uint64_t max_rounds, uint64_t* rounds_done) {
   if (rc) return rc;
   // a round still held (an earlier pool growth failed and the caller runs again): grow first
   if ((ctx->h_ctrl->hold || ctx->h_ctrl->spill_n) && (rc = resolve_hold(ctx))) return rc;
+  // (sgn_run_until: a round edge at or past Ctrl::pause_at holds with HOLD_PAUSE and the loops
+  // below stop on it; sgn_run itself runs with pause_at = EMU_MAX and never sees one)
+  ctx->paused = false;
   const uint64_t r_start = ctx->h_ctrl->rounds;
   uint64_t enq = 0;
   // Rounds are enqueued in batches with one host synchronisation per batch (the window
@@ -6139,7 +6154,7 @@ int sgn_run(sgn_ctx* ctx, uint64_t max_rounds, uint64_t* rounds_done) {
     bool fresh = true;
     // persistent rounds: one launch runs up to kPersistRounds rounds (grid barriers inside);
     // a launch ends early at a held round edge (a pool grows here, then the rounds go on)
-    while (ctx->h_ctrl->active && enq < max_rounds && ctx->persist_grid) {
+    while (ctx->h_ctrl->active && enq < max_rounds && ctx->persist_grid && !ctx->paused) {
       const uint32_t n = (uint32_t)std::min<uint64_t>(kPersistRounds, max_rounds - enq);
       // (no per-launch memsets: the launch resets its round buffers before its census)
       time_begin(ctx, K_EXECUTE);
@@ -6188,7 +6203,7 @@ int sgn_run(sgn_ctx* ctx, uint64_t max_rounds, uint64_t* rounds_done) {
   // (comm_complete_spill) turns the rest of its batch into no-ops, which are not rounds
   uint64_t done = ctx->h_ctrl->rounds - r_start;
   static const bool dbg = getenv("SGN_DEBUG_RUN") != nullptr;
-  while (ctx->h_ctrl->active && done < max_rounds) {
+  while (ctx->h_ctrl->active && done < max_rounds && !ctx->paused) {
     const uint64_t n = std::min<uint64_t>(batch, max_rounds - done);
     if (dbg)
       fprintf(stderr, "[sgn r%u] batch n=%llu done=%llu graph=%d gexec=%d gsz=%u xsz=%u spills=%llu\n", ctx->rank,
@@ -6236,6 +6251,31 @@ int sgn_run(sgn_ctx* ctx, uint64_t max_rounds, uint64_t* rounds_done) {
   }
   if (rounds_done) *rounds_done = ctx->h_ctrl->rounds - r_start;
   return 0;
+}
+
+int sgn_run_until(sgn_ctx* ctx, uint64_t t_emulated, uint64_t* rounds_done) {
+  if (rounds_done) *rounds_done = 0;
+  if (!ctx) return SGN_EINVAL;
+  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
+  if (ctx->nranks > 1 || ctx->comm_local)
+    return set_error(ctx, SGN_ESTATE, "sgn_run_until runs a single shard: a sharded context has no device-side pause "
+                                      "(its round edges are decided across shards)");
+  ctx->ctrl_fresh = false;
+  int rc = sync_ctrl(ctx);
+  if (rc) return rc;
+  // (the fork's rule, manager.rs:1372-1382: pause once min_next_event_time >= target — the window
+  // start IS that minimum, so a target at or below it pauses before anything runs)
+  if (!ctx->h_ctrl->active || t_emulated <= ctx->h_ctrl->ws) return 0;
+  // the round edges compare on the device (finalize_fused, k_rounds): no single-stepping, one
+  // persistent launch still runs many rounds and ends at the first edge at or past the target
+  SGN_HIP(ctx, hipMemcpy((char*)ctx->S.ctrl + offsetof(Ctrl, pause_at), &t_emulated, 8, hipMemcpyHostToDevice));
+  rc = sgn_run(ctx, ~0ull, rounds_done);
+  const uint64_t never = EMU_MAX;
+  const hipError_t e = hipMemcpy((char*)ctx->S.ctrl + offsetof(Ctrl, pause_at), &never, 8, hipMemcpyHostToDevice);
+  ctx->h_ctrl->pause_at = never;
+  ctx->paused = false;
+  if (!rc && e != hipSuccess) rc = hip_fail(ctx, e, "hipMemcpy(pause_at)");
+  return rc;
 }
 
 namespace {

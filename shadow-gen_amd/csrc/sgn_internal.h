@@ -149,6 +149,9 @@ struct Ctrl {
   uint32_t res_xverdict;
   uint64_t hold_need;
   uint64_t rnd_alloc, rnd_spill;  // per-round launches: the Outbox counters' target (unread)
+  // sgn_run_until: the single-shard round edges hold (HOLD_PAUSE) once the next window starts
+  // at or after this time; EMU_MAX = never (sgn_run, sgn_round)
+  uint64_t pause_at;
 };
 
 static_assert(offsetof(Ctrl, min_used) == offsetof(Ctrl, round_min) + 8,
@@ -161,6 +164,7 @@ enum : uint32_t {
   HOLD_XSLOT = 4u,  // persistent multi-shard: some shard sent a peer more runs than its inbox slot
                     // holds (the rest wait in the sender's spill area: the host moves them)
   HOLD_XGROW = 8u,  // persistent multi-shard: a round used more than half an inbox slot (grow)
+  HOLD_PAUSE = 16u, // single shard: the next window starts at or after Ctrl::pause_at (sgn_run_until)
 };
 
 enum : uint32_t {
@@ -664,6 +668,12 @@ struct sgn_ctx {
   uint64_t x_epoch = 0, x_grows = 0, x_over_rounds = 0, x_moved = 0, x_launches = 0;
   std::vector<uint32_t> x_G;   // every shard's host groups (its bins' rows), by rank
 
+  // snapshots (snapshot.hip): the ones this context still owns, and the simulation generation
+  // (sgn_sim_init count) that tags them — a snapshot of an earlier simulation is refused
+  std::vector<sgn_snapshot*> snapshots;
+  uint64_t sim_gen = 0;
+  bool paused = false;  // the last held round edge carried HOLD_PAUSE (sgn_run_until stops on it)
+
   ~sgn_ctx();
 };
 
@@ -706,6 +716,14 @@ int comm_xmove_spills(sgn_ctx* ctx, const std::vector<std::vector<EvRec>>& out,
                       std::vector<EvRec>* in);  // runs past an inbox slot, to their shards (collective)
 int comm_allreduce_max_u64(sgn_ctx* ctx, uint64_t* host_v, size_t n);  // (host values, collective)
 int inject_runs(sgn_ctx* ctx, const std::vector<EvRec>& runs);      // engine.hip: into the calendar
+// snapshot.hip's view of engine.hip: the control block to the host (overflow check), a held round
+// edge's pool growth, DevSim to the device after a pool moved, and the round kernels' shapes
+// (LDS table, persistent grid) for the calendar layout as it is now
+int ctrl_sync(sgn_ctx* ctx);
+int resolve_pools(sgn_ctx* ctx);
+int sim_upload(sgn_ctx* ctx);
+void round_kernels_resize(sgn_ctx* ctx);
+void snapshots_release(sgn_ctx* ctx);  // snapshot.hip: every snapshot the context still owns
 }  // namespace sgn
 
 // Every object of libsgn is compiled against this header. A library linked from objects built

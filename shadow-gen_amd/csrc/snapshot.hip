@@ -1,0 +1,593 @@
+// snapshot.hip — snapshot and restore of a running simulation (sgn_snapshot_*).
+//
+// A simulation is a set of device buffers plus a few host-side counters, and the engine is
+// bit-deterministic, so "restore, then run" reproduces the run that followed the save. Every
+// mutable buffer but one is copied whole; the event calendar — (NB + 1) * G slabs of CAP records
+// of 32 B, gigabytes at config D with a small fraction of them live — is PACKED on the device:
+// slab i's runs go to packed[off[i] ..), off the exclusive scan of the slab fills. The packed
+// form does not depend on the slab capacity, so a snapshot taken before the calendar was re-laid
+// out unpacks into the layout it recorded ("Snapshots").
+#include <algorithm>
+#include <cstring>
+
+#include "sgn_internal.h"
+
+using namespace sgn;
+
+// ---- device side ----------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kScanThreads = 256, kScanPer = 8, kScanTile = kScanThreads * kScanPer;
+constexpr uint32_t kWaveSlabs = 64;   // slabs per wave of the copy kernels (one per lane)
+constexpr uint32_t kCopyWaves = 4;    // waves per workgroup of the copy kernels
+
+// the runs of slab i that the snapshot holds: its fill, never more than the slab has room for
+// (at a resolved round edge nothing is in the spill area, so fill <= room; the bound keeps every
+// access inside the pool and the extension whatever the fill word holds)
+__device__ __forceinline__ uint32_t slab_runs(const uint32_t* __restrict__ slab_n, const uint64_t* __restrict__ ext,
+                                              uint32_t cap, uint64_t i) {
+  const uint32_t room = cap + (ext ? (uint32_t)(ext[i] >> 40) : 0u);
+  return min(slab_n[i], room);
+}
+
+// block-wide exclusive scan of one u64 per thread (kScanThreads threads); *total: the block's sum
+__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* sh, uint64_t* total) {
+  const uint32_t t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (uint32_t d = 1; d < kScanThreads; d <<= 1) {
+    const uint64_t a = t >= d ? sh[t - d] : 0;
+    __syncthreads();
+    sh[t] += a;
+    __syncthreads();
+  }
+  const uint64_t incl = sh[t];
+  *total = sh[kScanThreads - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+// scan, pass 1: the runs of each tile of kScanTile slabs
+__global__ __launch_bounds__(kScanThreads) void k_snap_tile_sums(const uint32_t* __restrict__ slab_n,
+                                                                 const uint64_t* __restrict__ ext, uint32_t cap,
+                                                                 uint64_t n_slabs, uint64_t* __restrict__ tsum) {
+  __shared__ uint64_t sh[kScanThreads];
+  const uint64_t base = (uint64_t)blockIdx.x * kScanTile;
+  uint64_t s = 0;
+  for (uint32_t k = 0; k < kScanPer; k++) {
+    const uint64_t i = base + (uint64_t)k * kScanThreads + threadIdx.x;
+    if (i < n_slabs) s += slab_runs(slab_n, ext, cap, i);
+  }
+  uint64_t tot;
+  (void)block_excl_scan(s, sh, &tot);
+  if (threadIdx.x == 0) tsum[blockIdx.x] = tot;
+}
+
+// scan, pass 2 (one workgroup): the tile sums to their exclusive prefix, in place; the grand
+// total to *total
+__global__ __launch_bounds__(kScanThreads) void k_snap_tile_scan(uint64_t* __restrict__ tsum, uint32_t n_tiles,
+                                                                 uint64_t* __restrict__ total) {
+  __shared__ uint64_t sh[kScanThreads];
+  uint64_t carry = 0;
+  for (uint32_t b = 0; b < n_tiles; b += kScanThreads) {
+    const uint32_t i = b + threadIdx.x;
+    const uint64_t v = i < n_tiles ? tsum[i] : 0;
+    uint64_t tot;
+    const uint64_t ex = block_excl_scan(v, sh, &tot);
+    if (i < n_tiles) tsum[i] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+
+// scan, pass 3: off[i] for every slab (a thread takes kScanPer consecutive slabs); off[n_slabs]
+// is the total, written by pass 2
+__global__ __launch_bounds__(kScanThreads) void k_snap_offsets(const uint32_t* __restrict__ slab_n,
+                                                               const uint64_t* __restrict__ ext, uint32_t cap,
+                                                               uint64_t n_slabs, const uint64_t* __restrict__ tsum,
+                                                               uint64_t* __restrict__ off) {
+  __shared__ uint64_t sh[kScanThreads];
+  const uint64_t first = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanPer;
+  uint32_t n[kScanPer];
+  uint64_t s = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kScanPer; k++) {
+    n[k] = first + k < n_slabs ? slab_runs(slab_n, ext, cap, first + k) : 0u;
+    s += n[k];
+  }
+  uint64_t tot;
+  uint64_t o = tsum[blockIdx.x] + block_excl_scan(s, sh, &tot);
+#pragma unroll
+  for (uint32_t k = 0; k < kScanPer; k++) {
+    if (first + k < n_slabs) off[first + k] = o;
+    o += n[k];
+  }
+}
+
+// The copy. A wave takes kWaveSlabs consecutive slabs, one per lane for the bookkeeping: their
+// packed runs are ONE contiguous range (off is a scan), which the wave walks in 16-byte units —
+// lane l moves unit u + l, so a full wave moves 1 KB of consecutive packed bytes per access and,
+// inside a slab's run list, 1 KB of consecutive pool bytes; a record is the two units 2r, 2r + 1.
+// The slab of a unit is found by a binary search over the 64 slab offsets in LDS. Empty and short
+// slabs cost their lane a table entry, not a wave, so a calendar of a million mostly empty slabs
+// is a few thousand waves of bookkeeping plus the live bytes. kPack: pool -> packed, else back.
+template <bool kPack>
+__global__ __launch_bounds__(kWaveSlabs * kCopyWaves) void k_snap_copy(
+    EvRec* __restrict__ pool, EvRec* __restrict__ ext_pool, const uint64_t* __restrict__ ext, uint32_t cap,
+    const uint64_t* __restrict__ off, uint64_t n_slabs, EvRec* __restrict__ packed) {
+  __shared__ uint32_t rel_[kCopyWaves][kWaveSlabs + 1];  // record offsets from the wave's first slab
+  __shared__ uint64_t eo_[kCopyWaves][kWaveSlabs];       // extension offsets (records into ext_pool)
+  const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t sb = ((uint64_t)blockIdx.x * kCopyWaves + wv) * kWaveSlabs;
+  uint32_t* rel = rel_[wv];
+  uint64_t* eo = eo_[wv];
+  uint64_t o0 = 0;
+  if (sb < n_slabs) {  // (the last workgroup's waves past the calendar only keep the barrier)
+    const uint64_t i = sb + lane;
+    // off has n_slabs + 1 entries: lanes past the calendar's end read the total
+    const uint64_t last = sb + kWaveSlabs < n_slabs ? sb + kWaveSlabs : n_slabs;
+    o0 = off[sb];
+    rel[lane] = (uint32_t)(off[i < last ? i : last] - o0);
+    if (lane == 0) rel[kWaveSlabs] = (uint32_t)(off[last] - o0);
+    eo[lane] = (ext && i < n_slabs) ? (ext[i] & EXT_OFF_MASK) : 0;
+  }
+  __syncthreads();
+  if (sb >= n_slabs) return;
+  const uint32_t tot = rel[kWaveSlabs];
+  uint4* pk = (uint4*)(packed + o0);
+  // where unit u of the wave's packed range lives in the calendar
+  auto locate = [&](uint64_t u) -> uint4* {
+    const uint32_t r = (uint32_t)(u >> 1), half = (uint32_t)(u & 1);
+    // the last slab s with rel[s] <= r (empty slabs share their successor's offset: skipped)
+    uint32_t lo = 0, hi = kWaveSlabs;  // invariant: rel[lo] <= r < rel[hi]
+#pragma unroll
+    for (uint32_t step = 0; step < 6; step++) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (rel[mid] <= r) lo = mid; else hi = mid;
+    }
+    const uint32_t j = r - rel[lo];
+    // (j < this slab's runs <= cap + its extension's capacity, by slab_runs)
+    EvRec* rec = j < cap ? pool + (sb + lo) * cap + j : ext_pool + eo[lo] + (j - cap);
+    return (uint4*)rec + half;
+  };
+  // two 16-byte accesses per lane and step, both loads issued before either store
+  const uint64_t nu = 2ull * tot;
+  uint64_t u = lane;
+  for (; u + 64 < nu; u += 128) {
+    uint4* p0 = locate(u);
+    uint4* p1 = locate(u + 64);
+    if (kPack) {
+      const uint4 a = *p0, b = *p1;
+      pk[u] = a;
+      pk[u + 64] = b;
+    } else {
+      const uint4 a = pk[u], b = pk[u + 64];
+      *p0 = a;
+      *p1 = b;
+    }
+  }
+  if (u < nu) {
+    uint4* p = locate(u);
+    if (kPack) pk[u] = *p; else *p = pk[u];
+  }
+}
+
+}  // namespace
+
+// ---- host side ------------------------------------------------------------------------------
+struct sgn_snapshot {
+  sgn_ctx* ctx = nullptr;
+  uint64_t gen = 0;
+  DevSim S{};   // the layout at save: CAP, cq_pages, spill_cap, ext_total, gspec (its pointers are
+                // the buffers of that time and are never followed)
+  Ctrl ctrl{};  // the control block at save
+  struct Buf {
+    void* d = nullptr;
+    size_t bytes = 0;
+  };
+  std::vector<Buf> fixed;                         // state_buffers() order
+  Buf codel, cq_next, cq_free, spill, spill_idx;  // the pools that grow
+  Buf drain;                                      // undrained records [0, drain_n)
+  Buf packed;                                     // the calendar's runs
+  uint64_t runs = 0;
+  // host-side simulation state
+  uint64_t rounds_enqueued = 0;
+  std::vector<uint64_t> handles;
+  std::vector<uint32_t> submit_seq;
+  std::vector<sgn_drain_rec> drain_held;
+  std::vector<uint64_t> h_ext;
+  uint64_t codel_grows = 0, cal_grows = 0, cal_spill_runs = 0, ext_slabs = 0, spill_grows = 0, rounds_held = 0,
+           codel_allocs_before = 0;
+  sgn_snapshot_info info{};
+};
+
+namespace {
+
+using Buf = sgn_snapshot::Buf;
+
+// The mutable buffers of DevSim that never move or change size after sgn_sim_init, in a fixed
+// order (null: this simulation has none). Decided field by field (DESIGN.md lists the rest):
+// constants (routing tables, hconst, sid_of, peer*, host_of, dns_*, servers, rank_lo) are not
+// state; the round buffers (rb_min, rb_keep, rb_cnt, rb_occ, fin_*) are idle at a round edge —
+// the per-round finalize exchanges them back to their reset values and a persistent launch resets
+// them itself before its census; rb_free is three words of that kind, saved anyway.
+std::vector<std::pair<void*, size_t>> state_buffers(const DevSim& S) {
+  const size_t nH = S.nH, n_slabs = (size_t)(S.NB + 1) * S.G;
+  std::vector<std::pair<void*, size_t>> v;
+  v.push_back({(void*)S.hrec, nH * sizeof(HostRec)});
+  v.push_back({(void*)S.htile, S.htile ? (nH + 63) / 64 * 8 * 64 * 16 : 0});
+  v.push_back({(void*)S.n_cnt, (size_t)N_CNT * nH * 8});
+  v.push_back({(void*)S.maxq, nH * 4});
+  v.push_back({(void*)S.nextloc, nH * 8});
+  v.push_back({(void*)S.npeer, S.npeer ? nH * 4 : 0});
+  v.push_back({(void*)S.rb_free, 3 * 8});
+  v.push_back({(void*)S.fifo, nH * (size_t)S.fifo_cap * sizeof(FifoEnt)});
+  v.push_back({(void*)S.fifo_addr, S.fifo_addr ? nH * (size_t)S.fifo_cap * 4 : 0});
+  v.push_back({(void*)S.slab_n, n_slabs * 4});
+  v.push_back({(void*)S.bucket_slab, (size_t)S.NB * 4});
+  v.push_back({(void*)S.bucket_min, (size_t)S.NB * 8});
+  v.push_back({(void*)S.w_cnt, (size_t)W_N * S.G * 8});
+  return v;
+}
+
+bool buf_alloc(Buf* b, size_t bytes) {
+  b->d = nullptr;
+  b->bytes = bytes;
+  return bytes == 0 || hipMalloc(&b->d, bytes) == hipSuccess;
+}
+void buf_free(Buf* b) {
+  if (b->d) (void)hipFree(b->d);
+  b->d = nullptr;
+  b->bytes = 0;
+}
+void snap_release(sgn_snapshot* s) {
+  for (Buf& b : s->fixed) buf_free(&b);
+  for (Buf* b : {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain, &s->packed}) buf_free(b);
+  delete s;
+}
+
+// the scan's scratch: off (n_slabs + 1 words, the last the total) and the tile sums
+struct Scan {
+  uint64_t* off = nullptr;
+  uint64_t* tsum = nullptr;
+  uint32_t n_tiles = 0;
+  ~Scan() {
+    if (off) (void)hipFree(off);
+    if (tsum) (void)hipFree(tsum);
+  }
+  bool alloc(uint64_t n_slabs) {
+    n_tiles = (uint32_t)((n_slabs + kScanTile - 1) / kScanTile);
+    return hipMalloc((void**)&off, (n_slabs + 1) * 8) == hipSuccess &&
+           hipMalloc((void**)&tsum, (size_t)std::max(1u, n_tiles) * 8) == hipSuccess;
+  }
+};
+// off = exclusive scan of the slab fills, stream-ordered
+void launch_scan(hipStream_t st, const Scan& sc, const uint32_t* slab_n, const uint64_t* ext, uint32_t cap,
+                 uint64_t n_slabs) {
+  hipLaunchKernelGGL(k_snap_tile_sums, dim3(sc.n_tiles), dim3(kScanThreads), 0, st, slab_n, ext, cap, n_slabs, sc.tsum);
+  hipLaunchKernelGGL(k_snap_tile_scan, dim3(1), dim3(kScanThreads), 0, st, sc.tsum, sc.n_tiles, sc.off + n_slabs);
+  hipLaunchKernelGGL(k_snap_offsets, dim3(sc.n_tiles), dim3(kScanThreads), 0, st, slab_n, ext, cap, n_slabs,
+                     (const uint64_t*)sc.tsum, sc.off);
+}
+template <bool kPack>
+void launch_copy(hipStream_t st, const Scan& sc, EvRec* pool, EvRec* ext_pool, const uint64_t* ext, uint32_t cap,
+                 uint64_t n_slabs, EvRec* packed) {
+  const uint64_t per_wg = (uint64_t)kWaveSlabs * kCopyWaves;
+  hipLaunchKernelGGL((k_snap_copy<kPack>), dim3((uint32_t)((n_slabs + per_wg - 1) / per_wg)),
+                     dim3(kWaveSlabs * kCopyWaves), 0, st, pool, ext_pool, ext, cap, (const uint64_t*)sc.off, n_slabs,
+                     packed);
+}
+
+int sharded(sgn_ctx* ctx, const char* what) {
+  return set_error(ctx, SGN_ESTATE, std::string(what) + ": a sharded context cannot be snapshotted (a multi-shard "
+                                        "snapshot needs a collective over every shard at one round edge)");
+}
+
+sgn_snapshot* owned(sgn_ctx* ctx, const sgn_snapshot* s) {
+  auto it = std::find(ctx->snapshots.begin(), ctx->snapshots.end(), s);
+  return it == ctx->snapshots.end() ? nullptr : *it;
+}
+
+}  // namespace
+
+void sgn::snapshots_release(sgn_ctx* ctx) {
+  for (sgn_snapshot* s : ctx->snapshots) snap_release(s);
+  ctx->snapshots.clear();
+}
+
+extern "C" {
+
+int sgn_snapshot_save(sgn_ctx* ctx, sgn_snapshot** out) {
+  if (out) *out = nullptr;
+  if (!ctx || !out) return ctx ? set_error(ctx, SGN_EINVAL, "sgn_snapshot_save: null argument") : SGN_EINVAL;
+  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
+  if (ctx->nranks > 1 || ctx->comm_local) return sharded(ctx, "sgn_snapshot_save");
+  SGN_HIP(ctx, hipSetDevice(ctx->device));
+  // CPU-held RNG states back to the device, then a resolved round edge (what sgn_run does on entry)
+  if (int e = rng_release(ctx)) return e;
+  int rc = ctrl_sync(ctx);
+  if (rc) return rc;
+  if (ctx->h_ctrl->hold || ctx->h_ctrl->spill_n) {
+    ctx->ctrl_fresh = false;
+    if ((rc = resolve_pools(ctx)) || (rc = ctrl_sync(ctx))) return rc;
+    ctx->paused = false;
+  }
+  const DevSim& S = ctx->S;
+  const Ctrl& c = *ctx->h_ctrl;
+  if (c.spill_n) return set_error(ctx, SGN_ESTATE, "sgn_snapshot_save: the calendar's spill area is not empty");
+  const uint64_t n_slabs = (uint64_t)(S.NB + 1) * S.G;
+  hipStream_t st = ctx->stream;
+
+  sgn_snapshot* s = new sgn_snapshot();
+  Scan sc;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  auto fail = [&](int code, const std::string& msg) {
+    (void)hipStreamSynchronize(st);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    snap_release(s);
+    return set_error(ctx, code, msg);
+  };
+  const char* oom = "device allocation failed (snapshot)";
+  for (hipEvent_t& e : ev)
+    if (hipEventCreate(&e) != hipSuccess) return fail(SGN_EDEVICE, "hipEventCreate failed (snapshot)");
+  // every buffer but the packed calendar (its size is the scan's result)
+  const auto src = state_buffers(S);
+  s->fixed.resize(src.size());
+  bool ok = sc.alloc(n_slabs);
+  for (size_t k = 0; ok && k < src.size(); k++) ok = buf_alloc(&s->fixed[k], src[k].second);
+  const size_t P = S.cq_pages;
+  const uint64_t nsp = std::min<uint64_t>(c.spill_n, S.spill_cap);
+  const uint64_t ndr = S.drain ? std::min<uint64_t>(c.drain_n, S.drain_cap) : 0;
+  ok = ok && buf_alloc(&s->codel, P * CQ_PAGE * sizeof(CodelEnt)) && buf_alloc(&s->cq_next, P * 4) &&
+       buf_alloc(&s->cq_free, P * 4) && buf_alloc(&s->spill, nsp * sizeof(EvRec)) && buf_alloc(&s->spill_idx, nsp * 4) &&
+       buf_alloc(&s->drain, ndr * sizeof(sgn_drain_rec));
+  if (!ok) return fail(SGN_ENOMEM, oom);
+
+  // the scan first: the host needs its total before it can size the packed section
+  (void)hipEventRecord(ev[0], st);
+  launch_scan(st, sc, (const uint32_t*)S.slab_n, (const uint64_t*)S.ext, S.CAP, n_slabs);
+  (void)hipEventRecord(ev[1], st);
+  uint64_t total = 0;
+  if (hipMemcpyAsync(&total, sc.off + n_slabs, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return fail(SGN_EDEVICE, "snapshot: the calendar scan failed");
+  if (total > n_slabs * S.CAP + S.ext_total) return fail(SGN_ESTATE, "snapshot: calendar fill above its capacity");
+  if (!buf_alloc(&s->packed, total * sizeof(EvRec))) return fail(SGN_ENOMEM, oom);
+  s->runs = total;
+
+  auto d2d = [&](Buf& b, const void* from) {
+    return b.bytes == 0 || hipMemcpyAsync(b.d, from, b.bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+  };
+  (void)hipEventRecord(ev[2], st);
+  if (total)  // (an empty calendar — a save right after sgn_sim_init — launches nothing)
+    launch_copy<true>(st, sc, (EvRec*)S.pool, (EvRec*)S.ext_pool, (const uint64_t*)S.ext, S.CAP, n_slabs,
+                      (EvRec*)s->packed.d);
+  (void)hipEventRecord(ev[3], st);
+  ok = hipGetLastError() == hipSuccess;
+  for (size_t k = 0; ok && k < src.size(); k++) ok = d2d(s->fixed[k], src[k].first);
+  ok = ok && d2d(s->codel, (const void*)S.codel) && d2d(s->cq_next, (const void*)S.cq_next) &&
+       d2d(s->cq_free, (const void*)S.cq_free) && d2d(s->spill, (const void*)S.spill) &&
+       d2d(s->spill_idx, (const void*)S.spill_idx) && d2d(s->drain, (const void*)S.drain);
+  hipEvent_t ev_end = nullptr;
+  ok = ok && hipEventCreate(&ev_end) == hipSuccess && hipEventRecord(ev_end, st) == hipSuccess;
+  ok = ok && hipStreamSynchronize(st) == hipSuccess;
+  float ms_scan = 0, ms_pack = 0, ms_rest = 0;
+  if (ok) {
+    (void)hipEventElapsedTime(&ms_scan, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&ms_pack, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&ms_rest, ev[3], ev_end);
+  }
+  if (ev_end) (void)hipEventDestroy(ev_end);
+  if (!ok) return fail(SGN_EDEVICE, "snapshot: a device copy failed");
+  for (hipEvent_t& e : ev) {
+    (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+
+  s->ctx = ctx;
+  s->gen = ctx->sim_gen;
+  s->S = S;
+  s->ctrl = c;
+  s->rounds_enqueued = ctx->rounds_enqueued;
+  s->handles = ctx->handles;
+  s->submit_seq = ctx->submit_seq;
+  s->drain_held = ctx->drain_held;
+  s->h_ext = ctx->h_ext;
+  s->codel_grows = ctx->codel_grows;
+  s->cal_grows = ctx->cal_grows;
+  s->cal_spill_runs = ctx->cal_spill_runs;
+  s->ext_slabs = ctx->ext_slabs;
+  s->spill_grows = ctx->spill_grows;
+  s->rounds_held = ctx->rounds_held;
+  s->codel_allocs_before = ctx->codel_allocs_before;
+  sgn_snapshot_info& in = s->info;
+  in.rounds = c.rounds;
+  in.window_start = c.ws;
+  in.window_end = c.we;
+  in.device_bytes = s->packed.bytes;
+  for (const Buf& b : s->fixed) in.device_bytes += b.bytes;
+  for (const Buf* b : {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain}) in.device_bytes += b->bytes;
+  in.host_bytes = sizeof(sgn_snapshot) + s->fixed.size() * sizeof(Buf) + s->handles.size() * 8 + s->submit_seq.size() * 4 +
+                  s->drain_held.size() * sizeof(sgn_drain_rec) + s->h_ext.size() * 8;
+  in.calendar_runs = total;
+  in.calendar_bytes = total * sizeof(EvRec);
+  in.calendar_pool_bytes = (n_slabs * S.CAP + S.ext_total) * sizeof(EvRec);
+  in.save_ms = (double)ms_scan + (double)ms_pack + (double)ms_rest;
+  in.pack_ms = (double)ms_scan + (double)ms_pack;
+  ctx->snapshots.push_back(s);
+  *out = s;
+  return 0;
+}
+
+int sgn_snapshot_restore(sgn_ctx* ctx, const sgn_snapshot* snap) {
+  if (!ctx || !snap) return ctx ? set_error(ctx, SGN_EINVAL, "sgn_snapshot_restore: null argument") : SGN_EINVAL;
+  sgn_snapshot* s = owned(ctx, snap);
+  if (!s) return set_error(ctx, SGN_EINVAL, "sgn_snapshot_restore: not a snapshot of this context");
+  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
+  if (ctx->nranks > 1 || ctx->comm_local) return sharded(ctx, "sgn_snapshot_restore");
+  if (s->gen != ctx->sim_gen)
+    return set_error(ctx, SGN_ESTATE, "sgn_snapshot_restore: the snapshot was taken before the last sgn_sim_init");
+  if (!ctx->failed.empty()) return set_error(ctx, SGN_ESTATE, "simulation unusable: " + ctx->failed);
+  SGN_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  SGN_HIP(ctx, hipStreamSynchronize(st));
+  DevSim& S = ctx->S;
+  const DevSim& Z = s->S;
+  const uint64_t n_slabs = (uint64_t)(S.NB + 1) * S.G;
+  // the launch sequence's words keep their live values (below): read them now
+  Ctrl live{};
+  SGN_HIP(ctx, hipMemcpy(&live, (const void*)S.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
+
+  // ---- the snapshot's pool layout: every buffer it needs that the context does not have at
+  // that size is allocated before anything changes (SGN_ENOMEM leaves the context as it was)
+  const bool codel_re = S.cq_pages != Z.cq_pages, spill_re = S.spill_cap != Z.spill_cap, cap_re = S.CAP != Z.CAP;
+  const bool ext_re = ctx->h_ext != s->h_ext;
+  const size_t P = Z.cq_pages;
+  CodelEnt* n_codel = nullptr;
+  uint32_t *n_next = nullptr, *n_free = nullptr, *n_sidx = nullptr;
+  EvRec *n_spill = nullptr, *n_pool = nullptr, *n_epool = nullptr;
+  uint64_t* n_ext = nullptr;
+  Scan sc;
+  bool ok = sc.alloc(n_slabs);
+  if (ok && codel_re) {
+    n_codel = (CodelEnt*)dev_alloc(ctx, P * CQ_PAGE * sizeof(CodelEnt), false);
+    n_next = (uint32_t*)dev_alloc(ctx, P * 4, false);
+    n_free = (uint32_t*)dev_alloc(ctx, P * 4, false);
+    ok = n_codel && n_next && n_free;
+  }
+  if (ok && spill_re) {
+    n_spill = (EvRec*)dev_alloc(ctx, Z.spill_cap * sizeof(EvRec), false);
+    n_sidx = (uint32_t*)dev_alloc(ctx, Z.spill_cap * 4, false);
+    ok = n_spill && n_sidx;
+  }
+  if (ok && cap_re) ok = (n_pool = (EvRec*)dev_alloc(ctx, n_slabs * Z.CAP * sizeof(EvRec), false)) != nullptr;
+  if (ok && ext_re && Z.ext_total) {
+    n_epool = (EvRec*)dev_alloc(ctx, Z.ext_total * sizeof(EvRec), false);
+    n_ext = (uint64_t*)dev_alloc(ctx, n_slabs * 8, false);
+    ok = n_epool && n_ext;
+  }
+  if (!ok) {
+    dev_free(ctx, n_codel, P * CQ_PAGE * sizeof(CodelEnt));
+    dev_free(ctx, n_next, P * 4);
+    dev_free(ctx, n_free, P * 4);
+    dev_free(ctx, n_spill, Z.spill_cap * sizeof(EvRec));
+    dev_free(ctx, n_sidx, Z.spill_cap * 4);
+    dev_free(ctx, n_pool, n_slabs * Z.CAP * sizeof(EvRec));
+    dev_free(ctx, n_epool, Z.ext_total * sizeof(EvRec));
+    dev_free(ctx, n_ext, n_slabs * 8);
+    return set_error(ctx, SGN_ENOMEM, "device allocation failed (snapshot restore)");
+  }
+  // ---- from here the context changes: the pools the run grew since go, the saved sizes return
+  ctx->ctrl_fresh = false;
+  ctx->rng_held.clear();  // (CPU-held draws belong to the state being replaced)
+  if (codel_re) {
+    dev_free(ctx, (void*)S.codel, (size_t)S.cq_pages * CQ_PAGE * sizeof(CodelEnt));
+    dev_free(ctx, (void*)S.cq_next, (size_t)S.cq_pages * 4);
+    dev_free(ctx, (void*)S.cq_free, (size_t)S.cq_pages * 4);
+    S.codel = (decltype(S.codel))n_codel;
+    S.cq_next = (decltype(S.cq_next))n_next;
+    S.cq_free = (decltype(S.cq_free))n_free;
+    S.cq_pages = Z.cq_pages;
+  }
+  if (spill_re) {
+    dev_free(ctx, (void*)S.spill, S.spill_cap * sizeof(EvRec));
+    dev_free(ctx, (void*)S.spill_idx, S.spill_cap * 4);
+    S.spill = (decltype(S.spill))n_spill;
+    S.spill_idx = (decltype(S.spill_idx))n_sidx;
+    S.spill_cap = Z.spill_cap;
+  }
+  if (cap_re) {
+    dev_free(ctx, (void*)S.pool, n_slabs * S.CAP * sizeof(EvRec));
+    S.pool = (decltype(S.pool))n_pool;
+    S.CAP = Z.CAP;
+  }
+  if (ext_re) {
+    if (S.ext_pool) dev_free(ctx, (void*)S.ext_pool, S.ext_total * sizeof(EvRec));
+    if (S.ext) dev_free(ctx, (void*)S.ext, n_slabs * 8);
+    S.ext_pool = (decltype(S.ext_pool))n_epool;
+    S.ext = (decltype(S.ext))n_ext;
+    S.ext_total = Z.ext_total;
+    ctx->h_ext = s->h_ext;
+    if (n_ext) SGN_HIP(ctx, hipMemcpy(n_ext, s->h_ext.data(), n_slabs * 8, hipMemcpyHostToDevice));
+  }
+  S.gspec = Z.gspec;
+  ctx->ext_slabs = s->ext_slabs;
+  const bool relaid = codel_re || spill_re || cap_re || ext_re;
+  if (cap_re) round_kernels_resize(ctx);  // the LDS table and the persistent grid follow the slab size
+  if (relaid) {
+    if (int rc = sim_upload(ctx)) {
+      ctx->failed = "sgn_snapshot_restore failed half way";
+      return rc;
+    }
+  } else {
+    drop_graph(ctx);
+  }
+
+  // ---- the state
+  auto d2d = [&](void* to, const Buf& b) {
+    return b.bytes == 0 || hipMemcpyAsync(to, b.d, b.bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+  };
+  const auto dst = state_buffers(S);
+  ok = dst.size() == s->fixed.size();
+  for (size_t k = 0; ok && k < dst.size(); k++) ok = dst[k].second == s->fixed[k].bytes && d2d(dst[k].first, s->fixed[k]);
+  ok = ok && d2d((void*)S.codel, s->codel) && d2d((void*)S.cq_next, s->cq_next) && d2d((void*)S.cq_free, s->cq_free) &&
+       d2d((void*)S.spill, s->spill) && d2d((void*)S.spill_idx, s->spill_idx) && d2d((void*)S.drain, s->drain);
+  if (ok && s->runs) {
+    // (the fills just restored, in stream order; the same scan as at save: the same offsets)
+    launch_scan(st, sc, (const uint32_t*)S.slab_n, (const uint64_t*)S.ext, S.CAP, n_slabs);
+    launch_copy<false>(st, sc, (EvRec*)S.pool, (EvRec*)S.ext_pool, (const uint64_t*)S.ext, S.CAP, n_slabs,
+                       (EvRec*)s->packed.d);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  // The control block as saved, except what belongs to the launch sequence and not to the
+  // simulation: the residency census (res_arrive counts every workgroup of every persistent
+  // launch since sgn_sim_init against sgn_ctx::res_base; the verdicts carry the launch epoch) and
+  // the barrier epoch. Rewinding them breaks the census arithmetic exactly as a memset would.
+  Ctrl c = s->ctrl;
+  c.res_arrive = live.res_arrive;
+  c.res_verdict = live.res_verdict;
+  c.res_xverdict = live.res_xverdict;
+  c.epoch = live.epoch;
+  c.hold = 0;
+  c.pause_at = EMU_MAX;
+  *ctx->h_ctrl = c;
+  ok = ok && hipMemcpyAsync((void*)S.ctrl, ctx->h_ctrl, sizeof(Ctrl), hipMemcpyHostToDevice, st) == hipSuccess;
+  ok = hipStreamSynchronize(st) == hipSuccess && ok;
+  if (!ok) {
+    ctx->failed = "sgn_snapshot_restore failed half way";
+    return set_error(ctx, SGN_EDEVICE, ctx->failed);
+  }
+  // ---- the host side of the simulation (the launch sequence — res_epoch, res_base, persist_off,
+  // persist_fallbacks — the kernel-time samples and the mirror's stale word stay as they are)
+  ctx->rounds_enqueued = s->rounds_enqueued;
+  ctx->handles = s->handles;
+  ctx->submit_seq = s->submit_seq;
+  ctx->drain_held = s->drain_held;
+  ctx->codel_grows = s->codel_grows;
+  ctx->cal_grows = s->cal_grows;
+  ctx->cal_spill_runs = s->cal_spill_runs;
+  ctx->spill_grows = s->spill_grows;
+  ctx->rounds_held = s->rounds_held;
+  ctx->codel_allocs_before = s->codel_allocs_before;
+  ctx->paused = false;
+  return 0;
+}
+
+void sgn_snapshot_free(sgn_ctx* ctx, sgn_snapshot* snap) {
+  if (!ctx || !snap) return;
+  auto it = std::find(ctx->snapshots.begin(), ctx->snapshots.end(), snap);
+  if (it == ctx->snapshots.end()) return;  // (another context's, or freed already)
+  ctx->snapshots.erase(it);
+  (void)hipSetDevice(ctx->device);
+  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  snap_release(snap);
+}
+
+int sgn_snapshot_info_get(const sgn_snapshot* snap, sgn_snapshot_info* out) {
+  if (!snap || !out) return SGN_EINVAL;
+  *out = snap->info;
+  return 0;
+}
+
+}  // extern "C"

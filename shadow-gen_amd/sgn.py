@@ -185,6 +185,12 @@ class EngineInfo(C.Structure):
         "persistent_x_launches", "persistent_x_grid")]
 
 
+class SnapshotInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "rounds", "window_start", "window_end", "device_bytes", "host_bytes", "calendar_runs",
+        "calendar_bytes", "calendar_pool_bytes")] + [("save_ms", C.c_double), ("pack_ms", C.c_double)]
+
+
 class KernelTimes(C.Structure):
     _fields_ = [("launches", C.c_uint64 * 16), ("ms", C.c_double * 16),
                 ("name", C.c_char_p * 16), ("n_kernels", C.c_uint32),
@@ -285,6 +291,11 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         "sgn_stage_push": (C.c_int, [vp, C.POINTER(PktSoa)]),
         "sgn_stage_pending": (C.c_uint64, [vp]),
         "sgn_stage_flush": (C.c_int, [vp]),
+        "sgn_run_until": (C.c_int, [vp, C.c_uint64, u64p]),
+        "sgn_snapshot_save": (C.c_int, [vp, C.POINTER(vp)]),
+        "sgn_snapshot_restore": (C.c_int, [vp, vp]),
+        "sgn_snapshot_free": (None, [vp, vp]),
+        "sgn_snapshot_info_get": (C.c_int, [vp, C.POINTER(SnapshotInfo)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -453,6 +464,33 @@ class Context:
         d = C.c_uint64()
         self.check(self.L.sgn_run(self.h, max_rounds, C.byref(d)))
         return d.value
+
+    # ---- run-control: run to a simulated time, snapshot, rewind (single shard) ----
+    def run_until(self, t_emulated):
+        """Whole windows until the next one would start at or after t_emulated (EmulatedTime);
+        returns the rounds run."""
+        d = C.c_uint64()
+        self.check(self.L.sgn_run_until(self.h, t_emulated, C.byref(d)))
+        return d.value
+
+    def snapshot_save(self):
+        """A handle to a snapshot of the simulation as it is now (owned by this context)."""
+        s = C.c_void_p()
+        self.check(self.L.sgn_snapshot_save(self.h, C.byref(s)))
+        return s
+
+    def snapshot_restore(self, snap):
+        self.check(self.L.sgn_snapshot_restore(self.h, snap))
+
+    def snapshot_free(self, snap):
+        self.L.sgn_snapshot_free(self.h, snap)
+
+    def snapshot_info(self, snap):
+        i = SnapshotInfo()
+        rc = self.L.sgn_snapshot_info_get(snap, C.byref(i))
+        if rc != 0:
+            raise SgnError(rc, "sgn_snapshot_info_get: null argument")
+        return {n: getattr(i, n) for n, _ in i._fields_}
 
     def stats(self):
         s = Stats()

@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""What a snapshot costs at bench.py's default sizes (one GPU): for configs C and D, one JSON
+line each with the save and restore times, the snapshot's size, the packed-copy rate of the
+calendar, the time a raw device-to-device copy of the unpacked calendar takes in the same process
+(what a snapshot without packing would pay for the calendar alone), and the only way back there
+was before snapshots: sgn_sim_init + sgn_run to the same round.
+
+usage: python tools/snapshot_timing.py [--workload C D] [--rounds 1500] [--out FILE]
+The save is taken after bench.py's warm-up + steps worth of rounds (5 + 10 steps of 100)."""
+import argparse
+import json
+import pathlib
+import sys
+import time
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "shadow-gen_amd"))
+
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+import sgn  # noqa: E402
+
+
+def workload(name, rounds):
+    if name == "C":
+        return bench.build_workload(100_000, 1000)
+    n = 1_000_000
+    g, used, hosts, cfg, tr = bench.build_workload_d(n, 1000, stop_ns=max(1_000_000_000, (rounds + 100) * 1_000_000))
+    cfg.event_capacity = 257 * (-(-n // 64)) * 128  # bench.py's slabs for D
+    return g, used, hosts, cfg, tr
+
+
+def raw_copy_ms(nbytes):
+    """A device-to-device copy of nbytes (the second of two: the first touches the pages)."""
+    a = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    b = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    a.zero_()
+    b.copy_(a)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    b.copy_(a)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1)
+    del a, b
+    torch.cuda.empty_cache()
+    return ms
+
+
+def measure(name, rounds):
+    g, used, hosts, cfg, tr = workload(name, rounds)
+    c = sgn.Context(device=0)
+    c.routes_build(g, used)
+    c.hosts_set(hosts)
+    c.sim_init(cfg, tr)
+    done = c.run(rounds)
+    w = c.window()
+    snap = c.snapshot_save()
+    c.snapshot_free(snap)
+    snap = c.snapshot_save()  # (the second save: allocations and code objects warm)
+    info = c.snapshot_info(snap)
+    c.run(200)
+    t0 = time.perf_counter()
+    c.snapshot_restore(snap)  # (synchronises its stream before it returns)
+    restore_ms = (time.perf_counter() - t0) * 1e3
+    assert c.window() == w and c.stats()["rounds"] == done
+    eng = c.engine_info()
+    c.snapshot_free(snap)
+    raw_ms = raw_copy_ms(info["calendar_pool_bytes"])
+    t0 = time.perf_counter()
+    c.sim_init(cfg, tr)
+    init_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    c.run(done)
+    assert c.window() == w
+    rerun_ms = (time.perf_counter() - t0) * 1e3
+    c.close()
+    return {
+        "tool": "snapshot_timing", "build_id": sgn.build_id(), "workload": name, "hosts": hosts.n,
+        "rounds_at_save": done, "save_ms": round(info["save_ms"], 3), "pack_ms": round(info["pack_ms"], 3),
+        "restore_wall_ms": round(restore_ms, 3), "device_bytes": info["device_bytes"],
+        "host_bytes": info["host_bytes"], "calendar_runs": info["calendar_runs"],
+        "calendar_bytes": info["calendar_bytes"], "calendar_pool_bytes": info["calendar_pool_bytes"],
+        "pack_gb_per_s": round(info["calendar_bytes"] / max(info["pack_ms"], 1e-6) / 1e6, 2),
+        "raw_pool_copy_ms": round(raw_ms, 3),
+        "raw_pool_copy_gb_per_s": round(info["calendar_pool_bytes"] / max(raw_ms, 1e-6) / 1e6, 2),
+        "reinit_ms": round(init_ms, 1), "rerun_ms": round(rerun_ms, 1),
+        "slab_capacity": eng["slab_capacity"], "sim_device_bytes": eng["device_bytes"],
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", nargs="+", choices=("C", "D"), default=["C", "D"])
+    ap.add_argument("--rounds", type=int, default=1500)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lines = [json.dumps(measure(w, args.rounds)) for w in args.workload]
+    for ln in lines:
+        print(ln, flush=True)
+    if args.out:
+        pathlib.Path(args.out).write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
