@@ -262,12 +262,6 @@ __device__ __forceinline__ void cnt_add(SGN_GLB uint64_t* p, uint64_t v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// a / b for a divisor below 2^32: u32 division when the dividend fits too
-__device__ __forceinline__ uint64_t div_small(uint64_t a, uint64_t b) {
-  if (((a | b) >> 32) == 0) return (uint32_t)a / (uint32_t)b;
-  return a / b;
-}
-
 __device__ __forceinline__ uint32_t bucket_of(const DevSim& S, uint64_t t) {
   return (uint32_t)S.bw_div.div(t - SIM_START) & (S.NB - 1);
 }
@@ -1021,15 +1015,19 @@ struct HostExec {
   }
 
   // ---- TokenBucket::comforming_remove (network/relay/token_bucket.rs:65-154) ----
+  // n comforming_remove(dec) calls at one `now`, n >= 1 packets of one wire length: how many
+  // conform. Only the first call can refill (`now` does not move), so after it balance / dec
+  // conform in all; when fewer than n do, *dur is the conforming duration the first refused
+  // call returns. One instance of the refill and one of the duration per call site.
   template <int W>
-  __device__ __forceinline__ bool tb_remove(uint64_t dec, uint64_t* dur) {
+  __device__ __forceinline__ uint32_t tb_take(uint64_t dec, uint32_t n, uint64_t* dur) {
     DGT_BEGIN(tt);
-    const bool ok = tb_remove_<W>(dec, dur);
+    const uint32_t m = tb_take_<W>(dec, n, dur);
     DGT_END(DGT_TBRM, tt);
-    return ok;
+    return m;
   }
   template <int W>
-  __device__ __forceinline__ bool tb_remove_(uint64_t dec, uint64_t* dur) {
+  __device__ __forceinline__ uint32_t tb_take_(uint64_t dec, uint32_t n, uint64_t* dur) {
     uint64_t& bal = W == 0 ? tbb0 : tbb1;
     uint64_t& last = W == 0 ? tbl0 : tbl1;
     const uint64_t interval = 1000000ULL;  // relay/mod.rs:279
@@ -1048,33 +1046,23 @@ struct HostExec {
       last = emu_sat_add(last, adv);
       span = now - last;
     }
-    uint64_t next_refill_span = interval - span;
-    if (dec > bal) {
-      // compute_conforming_duration (:91-117)
-      const uint64_t inc = lr().tbc[W];
-      uint64_t req = dec - bal;
-      uint64_t n;
-      if (((req | inc) >> 32) == 0) {  // u32 division: the u64 routine is long
-        const uint32_t r32 = (uint32_t)req, i32 = (uint32_t)inc;
-        const uint32_t q = r32 / i32;
-        n = q + (r32 - q * i32 ? 1 : 0);
-      } else {
-        n = req / inc + ((req % inc) ? 1 : 0);
-      }
-      if (n == 0)
-        *dur = 0;
-      else if (n == 1)
+    const uint32_t m = tb_conforming(bal, dec, n);
+    bal -= (uint64_t)m * dec;
+    if (m < n) {
+      // compute_conforming_duration (:91-117) of the refused removal: dec > bal, so
+      // 0 < req <= dec and at least one refill is needed (tb_refills: never 0)
+      const uint64_t next_refill_span = interval - span;
+      const uint64_t nr = tb_refills(dec - bal, lr().tbc[W]);
+      if (nr == 1)
         *dur = next_refill_span;
       else {
-        uint64_t m = mul_sat(interval, n - 1, SIMTIME_MAX);
-        uint64_t s = next_refill_span + m;
+        uint64_t a = mul_sat(interval, nr - 1, SIMTIME_MAX);
+        uint64_t s = next_refill_span + a;
         if (s < next_refill_span || s > SIMTIME_MAX) s = SIMTIME_MAX;
         *dur = s;
       }
-      return false;
     }
-    bal -= dec;
-    return true;
+    return m;
   }
 
   // sgn_drun_{flush,add}_{seq,same} (sgn_workload.h) over LaneLDS::run / rn
@@ -1160,7 +1148,7 @@ struct HostExec {
     const uint64_t i = __hip_atomic_fetch_add(&C->pg_alloc, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     cnt_add(ob->pg_allocd, 1);
     if (i >= ob->pg_avail) return NO_HOST;
-    const uint32_t pg = ld_dev(&S.cq_free[i % S.cq_pages]);
+    const uint32_t pg = ld_dev(&S.cq_free[umod64(S.div_cq, i, S.cq_pages)]);
 #ifdef SGN_DIAG
     DGT_WAIT();
     DGT_END(DGT_CQALLOC, ta);
@@ -1170,7 +1158,7 @@ struct HostExec {
   __device__ __forceinline__ void cq_free_page(uint32_t pg) {
     DGT_BEGIN(tf);
     const uint64_t j = __hip_atomic_fetch_add(&C->pg_tail, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    st_dev(&S.cq_free[j % S.cq_pages], pg);
+    st_dev(&S.cq_free[umod64(S.div_cq, j, S.cq_pages)], pg);
     cnt_add(ob->pg_freed, 1);
     DGT_END(DGT_CQFREE, tf);
   }
@@ -1463,20 +1451,8 @@ struct HostExec {
             uint32_t m = n;
             bool blocked = false;
             if (!boot) {
-              if (!tb_remove<1>(wire, dur)) {
-                m = 0;
-                blocked = true;
-              } else if (n > 1) {
-                const uint64_t more = div_small(tbb1, wire);
-                if (more >= n - 1) {
-                  tbb1 -= (uint64_t)(n - 1) * wire;
-                } else {
-                  tbb1 -= more * wire;
-                  m = 1 + (uint32_t)more;
-                  blocked = true;
-                  tb_remove<1>(wire, dur);  // fails: same `now`, gives the conforming duration
-                }
-              }
+              m = tb_take<1>(wire, n, dur);
+              blocked = m < n;
             }
             const uint32_t used = m + (blocked ? 1u : 0u);
             const CodelEnt r = L->hd;
@@ -1518,7 +1494,7 @@ struct HostExec {
         DG(DG_FQLOAD);
       }
       // the source address is the router's (0.0.0.0), never this host's: no local bypass
-      if (!boot && !tb_remove<1>((uint64_t)p.payload + sgn_header_bytes(p.tag), dur)) {
+      if (!boot && tb_take<1>((uint64_t)p.payload + sgn_header_bytes(p.tag), 1, dur) == 0) {
         fl |= F_RI_NEXT;
         ri_src = p.src;
         ri_pay = p.payload;
@@ -1855,50 +1831,34 @@ struct HostExec {
     const bool boot = now < S.boot_end;
     uint64_t dur = 0;
     bool blocked = false;
-    if (fl & F_RO_NEXT) {
-      fl &= ~F_RO_NEXT;
-      const bool is_local = ro_dst == gid;
-      if (!boot && !is_local && !tb_remove<0>((uint64_t)ro_pay + sgn_header_bytes(ro_tag), &dur)) {
-        fl |= F_RO_NEXT;
-        blocked = true;
+    // the cached packet, or the head entry's run: one instance of the bucket and of the send
+    // for both (the cached packet is a run of one that is not in the queue)
+    const bool cached = (fl & F_RO_NEXT) != 0;
+    if (cached || fq_len > 0) {
+      FifoEnt e;
+      bool rr = false;
+      uint32_t run = 1, payload;
+      if (cached) {
+        fl &= ~F_RO_NEXT;
+        e.dst = ro_dst;
+        e.tag = ro_tag;
+        e.count = 1;
+        payload = ro_pay;
       } else {
-        Pkt p;
-        p.src = gid;
-        p.dst_ip = my_ip;
-        p.payload = ro_pay;
-        p.tag = ro_tag;
-        p.eid = 0;
-        if (is_local)
-          deliver_local(p);
-        else
-          send_batch(ro_dst, ro_pay, ro_tag, 1);
+        e = fifo_head();
+        // round-robin qdisc with other sockets waiting: one packet, then this socket goes to
+        // the back (NetworkInterface::pop, interface.rs:216-256); otherwise the leading
+        // datagrams of the train that share a payload size
+        rr = S.qdisc_rr && fq_len > 1;
+        run = (e.count == 1 || rr) ? 1u : e.count - 1;
+        payload = e.count == 1 ? (e.pay >> 16) : (e.pay & 0xFFFFu);
       }
-    } else if (fq_len > 0) {
-      const FifoEnt e = fifo_head();
-      // round-robin qdisc with other sockets waiting: one packet, then this socket goes to
-      // the back (NetworkInterface::pop, interface.rs:216-256); otherwise the leading
-      // datagrams of the train that share a payload size
-      const bool rr = S.qdisc_rr && fq_len > 1;
-      const uint32_t run = (e.count == 1 || rr) ? 1u : e.count - 1;
-      const uint32_t payload = e.count == 1 ? (e.pay >> 16) : (e.pay & 0xFFFFu);
       const uint64_t wire = (uint64_t)payload + sgn_header_bytes(e.tag);
       const bool is_local = e.dst == gid;
       uint32_t n_ok = run;
       if (!boot && !is_local) {
-        if (!tb_remove<0>(wire, &dur)) {
-          n_ok = 0;
-          blocked = true;
-        } else if (run > 1) {
-          const uint64_t more = div_small(tbb0, wire);
-          if (more >= run - 1) {
-            tbb0 -= (uint64_t)(run - 1) * wire;
-          } else {
-            tbb0 -= more * wire;
-            n_ok = 1 + (uint32_t)more;
-            blocked = true;
-            tb_remove<0>(wire, &dur);  // fails: same `now`, gives the conforming duration
-          }
-        }
+        n_ok = tb_take<0>(wire, run, &dur);
+        blocked = n_ok < run;
       }
       if (is_local) {
         Pkt p;
@@ -1908,16 +1868,18 @@ struct HostExec {
         p.tag = e.tag;
         p.eid = 0;
         for (uint32_t j = 0; j < n_ok; j++) {
-          if (tr()) trace_pop(gid, payload, e.tag);
+          if (tr() && !cached) trace_pop(gid, payload, e.tag);
           deliver_local(p);
         }
       } else {
-        send_batch(e.dst, payload, e.tag, n_ok, true);
+        send_batch(e.dst, payload, e.tag, n_ok, !cached);  // (the cached packet was popped before)
       }
       // the packet the bucket refused was popped too: it waits in Relay::next_packet
-      if (tr() && blocked) trace_pop(e.dst, payload, e.tag);
+      if (tr() && blocked && !cached) trace_pop(e.dst, payload, e.tag);
       const uint32_t consumed = n_ok + (blocked ? 1u : 0u);
-      if (consumed == e.count) {
+      if (cached) {
+        // not in the send queue
+      } else if (consumed == e.count) {
         fq_head = fq_head + 1 == S.fifo_cap ? 0 : fq_head + 1;
         fq_len--;
         if (fq_len == 0) fq_head = 0;  // (an empty queue's head is 0: an idle host's default)
@@ -2356,11 +2318,13 @@ struct ExecLDS {
 // arrival goes there, so its wait covers only what other workgroups read.
 // kXb (k_rounds_x): the group's inbox bins (the runs other shards sent it last round) are read in
 // the round trip of its first gather and taken into the calendar (see take_bins).
-template <bool kTrace, uint32_t kApp, bool kBig, bool kXb = false, typename AtEnd>
+template <bool kTrace, uint32_t kApp, bool kBig, bool kXb = false, bool kDiag = true, typename AtEnd>
 __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t ws, uint64_t we, uint32_t ks,
                            const ExecLDS& X, uint64_t* kmin_out, uint64_t* next_out,
                            AtEnd&& at_end) {
   SGN_GLB Ctrl* C = S.ctrl;
+  // per-wave diagnostics (SGN_STAMPS): compiled out of the kernels launched without them
+  SGN_GLB uint64_t* const stamps = kDiag ? S.stamps : nullptr;
   EvRec* lev = X.lev;
   uint16_t* lb = X.lb;
   uint16_t* lc = X.lc;
@@ -2375,12 +2339,12 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
   const uint32_t bs = bucket_of(S, ws), be = bucket_of(S, we - 1);
   const uint32_t nbk = ((be + S.NB - bs) & (S.NB - 1)) + 1;  // buckets overlapping the window
   const uint32_t gbase = S.lo + (g << S.gsh);  // HostId of lane 0
-  const uint64_t clk0 = S.stamps ? __builtin_amdgcn_s_memtime() : 0;
+  const uint64_t clk0 = stamps ? __builtin_amdgcn_s_memtime() : 0;
 #ifdef SGN_DIAG
-  if (S.stamps && lane < 32) S.stamps[SGN_STAMP_WORDS * (size_t)g + 48 + lane] = 0;
+  if (stamps && lane < 32) stamps[SGN_STAMP_WORDS * (size_t)g + 48 + lane] = 0;
   __syncthreads();
 #endif
-  const uint64_t rt0 = S.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
+  const uint64_t rt0 = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
   const size_t ik = (size_t)ks * S.G + g;
   SGN_GLB EvRec* pk = S.pool + ik * S.CAP;
 
@@ -2730,7 +2694,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
     return __ballot(slow) != 0;
   };
   for (uint32_t bi = 0; bi < nbk; bi++) {
-    const uint64_t c0 = S.stamps ? __builtin_amdgcn_s_memtime() : 0;
+    const uint64_t c0 = stamps ? __builtin_amdgcn_s_memtime() : 0;
     const uint32_t b = (bs + bi) & (S.NB - 1);
     bool last = bi == nbk - 1;
     uint64_t sub_end = last ? we : SIM_START + (S.bw_div.div(ws - SIM_START) + bi + 1) * S.BW;
@@ -2874,7 +2838,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
     if (early && !big) ex.prefetch_route();
     __syncthreads();
     // ---- 3. execute the sub-window [.., sub_end) (a big slab's piece: up to its bound) ----
-    const uint64_t c1 = S.stamps ? __builtin_amdgcn_s_memtime() : 0;
+    const uint64_t c1 = stamps ? __builtin_amdgcn_s_memtime() : 0;
 #ifdef SGN_DIAG
     // wave-level phase times (the loads are drained inside the load phase here)
     const bool go = valid && (cnt > 0 || (loaded ? ex.next_local_time() : lmin) < until);
@@ -2902,7 +2866,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
     // a big slab's host that ran in an earlier piece closes its digest runs with the last one
     if (big && fin && !go && loaded) ex.flush_digests();
     __syncthreads();  // LDS is reused by the next piece or bucket
-    if (S.stamps) {
+    if (stamps) {
       const uint64_t c2 = __builtin_amdgcn_s_memtime();
       t_gather += c1 - c0;
       t_exec += c2 - c1;
@@ -2973,7 +2937,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   const uint64_t w_store = __builtin_amdgcn_s_memtime() - td;
 #endif
-  if (S.stamps) {
+  if (stamps) {
     // per-wave diagnostics: shader cycles, total and max events over the wave's lanes
     const uint64_t clk1 = __builtin_amdgcn_s_memtime();
     uint32_t sum = n_ev, mx = n_ev;
@@ -2983,7 +2947,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
       mx = o > mx ? o : mx;
     }
     const uint32_t busy = __popcll(__ballot(n_ev > 0));
-    SGN_GLB uint64_t* st = S.stamps + SGN_STAMP_WORDS * (size_t)g;
+    SGN_GLB uint64_t* st = stamps + SGN_STAMP_WORDS * (size_t)g;
     if (lane == 0) {
       st[0] = clk1 - clk0;
       st[1] = sum;
@@ -3379,9 +3343,9 @@ __device__ __forceinline__ uint32_t census(SGN_GLB Ctrl* C, uint32_t P, uint32_t
   return v & 3u;
 }
 
-template <uint32_t kApp, bool kBig>
-__global__ __launch_bounds__(64, 2) void k_rounds(const DevSim* __restrict__ Sg, uint32_t max_rounds, uint32_t epoch,
-                                                  uint32_t res_base) {
+template <uint32_t kApp, bool kBig, bool kDiag>
+__device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint32_t max_rounds, uint32_t epoch,
+                                            uint32_t res_base) {
   const DevSim& S = *Sg;
   SGN_GLB Ctrl* C = S.ctrl;
   SGN_EXEC_LDS(X)
@@ -3491,7 +3455,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds(const DevSim* __restrict__ Sg,
     }
     // diagnostics (SGN_STAMPS): per round of this launch, {earliest start, latest arrival,
     // round edge known} on the 100 MHz clock
-    SGN_GLB uint64_t* rd = S.rdbg ? S.rdbg + 3 * (size_t)(r & 127) : nullptr;
+    SGN_GLB uint64_t* rd = kDiag && S.rdbg ? S.rdbg + 3 * (size_t)(r & 127) : nullptr;
     if (rd && threadIdx.x == 0)
       __hip_atomic_fetch_min(rd, (unsigned long long)__builtin_amdgcn_s_memrealtime(),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3508,7 +3472,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds(const DevSim* __restrict__ Sg,
     for (uint32_t g = gq0; g < gq1; g += gqs) {
       uint64_t kmin, m;
       const bool lastg = g + gqs >= gq1;  // the workgroup's last group arrives
-      exec_group<false, kApp, kBig>(S, g, ws, we, ks, X, &kmin, &m, [&](uint64_t k, uint64_t n, uint64_t od) {
+      exec_group<false, kApp, kBig, false, kDiag>(S, g, ws, we, ks, X, &kmin, &m, [&](uint64_t k, uint64_t n, uint64_t od) {
         kall = k < kall ? k : kall;
         mall = n < mall ? n : mall;
         oall += od;
@@ -3636,6 +3600,20 @@ __global__ __launch_bounds__(64, 2) void k_rounds(const DevSim* __restrict__ Sg,
       if (threadIdx.x == 0) st_sys(&S.ctrl_mirror[NW], (uint64_t)epoch);
     }
   }
+}
+
+// The product kernel, and its twin with the diagnostics (SGN_STAMPS: per-wave stamps, the
+// per-round timeline). The stamps' clocks, accumulators and pointers stay live across the event
+// loop, where the product kernel has no scalar register to spare.
+template <uint32_t kApp, bool kBig>
+__global__ __launch_bounds__(64, 2) void k_rounds(const DevSim* __restrict__ Sg, uint32_t max_rounds, uint32_t epoch,
+                                                  uint32_t res_base) {
+  rounds_body<kApp, kBig, false>(Sg, max_rounds, epoch, res_base);
+}
+template <uint32_t kApp, bool kBig>
+__global__ __launch_bounds__(64, 2) void k_rounds_diag(const DevSim* __restrict__ Sg, uint32_t max_rounds,
+                                                       uint32_t epoch, uint32_t res_base) {
+  rounds_body<kApp, kBig, true>(Sg, max_rounds, epoch, res_base);
 }
 
 // ---- persistent multi-shard rounds (k_rounds_x) ----
@@ -4685,8 +4663,15 @@ const void* execute_fn_t(uint32_t kind) {
 const void* execute_fn(uint32_t kind, bool trace) {
   return trace ? execute_fn_t<true>(kind) : execute_fn_t<false>(kind);
 }
+// (the twin with the diagnostics when the simulation starts with SGN_STAMPS set)
+bool rounds_diag() { return getenv("SGN_STAMPS") != nullptr; }
 template <bool kBig>
 const void* rounds_fn_t(uint32_t kind) {
+  if (rounds_diag()) {
+    if (kind == SGN_TRAFFIC_TGEN) return (const void*)k_rounds_diag<SGN_TRAFFIC_TGEN, kBig>;
+    if (kind == SGN_TRAFFIC_EXTERNAL) return (const void*)k_rounds_diag<SGN_TRAFFIC_EXTERNAL, kBig>;
+    return (const void*)k_rounds_diag<SGN_TRAFFIC_PERIODIC, kBig>;
+  }
   if (kind == SGN_TRAFFIC_TGEN) return (const void*)k_rounds<SGN_TRAFFIC_TGEN, kBig>;
   if (kind == SGN_TRAFFIC_EXTERNAL) return (const void*)k_rounds<SGN_TRAFFIC_EXTERNAL, kBig>;
   return (const void*)k_rounds<SGN_TRAFFIC_PERIODIC, kBig>;
@@ -4722,6 +4707,15 @@ void launch_k_rounds_t(sgn_ctx* ctx, uint32_t n) {
   // (the census: this launch's epoch, and the arrivals of the launches before it)
   const uint32_t ep = ++ctx->res_epoch, base = ctx->res_base;
   ctx->res_base += ctx->persist_grid;
+  if (ctx->S.stamps) {  // (SGN_STAMPS at sgn_sim_init: the twin that writes them)
+    if (k == SGN_TRAFFIC_TGEN)
+      hipLaunchKernelGGL((k_rounds_diag<SGN_TRAFFIC_TGEN, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
+    else if (k == SGN_TRAFFIC_EXTERNAL)
+      hipLaunchKernelGGL((k_rounds_diag<SGN_TRAFFIC_EXTERNAL, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
+    else
+      hipLaunchKernelGGL((k_rounds_diag<SGN_TRAFFIC_PERIODIC, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
+    return;
+  }
   if (k == SGN_TRAFFIC_TGEN)
     hipLaunchKernelGGL((k_rounds<SGN_TRAFFIC_TGEN, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
   else if (k == SGN_TRAFFIC_EXTERNAL)
@@ -5074,6 +5068,7 @@ int grow_codel(sgn_ctx* ctx, uint64_t extra) {
   S.cq_next = (decltype(S.cq_next))nn;
   S.cq_free = (decltype(S.cq_free))nf;
   S.cq_pages = (uint32_t)P2;
+  S.div_cq.init(P2);
   ctx->codel_allocs_before += c.pg_alloc;
   c.pg_alloc = 0;
   c.pg_tail = c.pg_avail = nfree;
@@ -5666,6 +5661,7 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
     const uint64_t pages = std::max<uint64_t>((uint64_t)nH + 64, ((uint64_t)nH * cfg->codel_cap + CQ_PAGE - 1) / CQ_PAGE);
     if (pages >= (1ULL << 28)) return set_error(ctx, SGN_EINVAL, "codel_cap: CoDel page pool above 2^28 pages");
     S.cq_pages = (uint32_t)pages;
+    S.div_cq.init(pages);
   }
   S.trace_on = ctx->trace_cap > 0;
   S.tkind = tr->kind;

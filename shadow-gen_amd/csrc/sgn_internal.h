@@ -308,6 +308,54 @@ struct UDiv64 {
   }
 };
 
+// ---- the event path's divisions, none of them the general u64 routine (~140 instructions
+// per inlined copy). Host and device alike; tests/native/event_arith_check.cpp compares them
+// with plain / and %. ----
+
+// x mod n for the run-time invariant n that d was made from: exact for every u64 x
+__host__ __device__ __forceinline__ uint64_t umod64(const UDiv64& d, uint64_t x, uint64_t n) {
+  return x - d.div(x) * n;
+}
+
+// The packet sizes the token buckets see: payload_len <= 65535 is enforced wherever a payload
+// enters (sgn_sim_init: payload_len, req_payload; sgn_submit; a TGEN response segment is at
+// most SGN_TGEN_MSS), and a header is at most 44 bytes (sgn_header_bytes).
+constexpr uint64_t TB_WIRE_MAX = 65535u + 44u;
+
+// TokenBucket::compute_conforming_duration's refill count ceil(req / inc) (token_bucket.rs:
+// 91-117) for 0 < req <= TB_WIRE_MAX, inc > 0. req is what a refused removal of `dec` tokens
+// lacks, dec - balance with balance < dec, and dec is one packet's wire length, so req < 2^32
+// always and the u32 quotient is exact. A bucket with inc >= 2^32 refills more than any
+// packet needs: 0 < req < inc, one refill.
+__host__ __device__ __forceinline__ uint64_t tb_refills(uint64_t req, uint64_t inc) {
+  if (inc >> 32) return 1;
+  const uint32_t r32 = (uint32_t)req, i32 = (uint32_t)inc;
+  const uint32_t q = r32 / i32;
+  return (uint64_t)q + (r32 - q * i32 ? 1 : 0);
+}
+
+// bal / dec for a bucket balance bal < 2^53 (a balance is at most inc + MTU with inc <=
+// 2^64 / 8000, sgn_sim_init) and a wire length 0 < dec < 2^32. Below 2^32 it is the u32
+// quotient. Above (only a bucket of >= 34 Tbit/s holds that much), the f64 quotient of two
+// exactly represented integers is within one of the true one whatever the rounding, and the
+// two multiplications put it right.
+__host__ __device__ __forceinline__ uint64_t tb_quot(uint64_t bal, uint64_t dec) {
+  if ((bal >> 32) == 0) return (uint32_t)bal / (uint32_t)dec;
+  uint64_t q = (uint64_t)((double)bal / (double)dec);
+  if (q * dec > bal)
+    q--;
+  else if (bal - q * dec >= dec)
+    q++;
+  return q;
+}
+
+// How many of n removals of dec tokens each a balance bal covers: min(n, bal / dec), decided
+// without dividing when all n conform (n * dec < 2^49: no overflow).
+__host__ __device__ __forceinline__ uint32_t tb_conforming(uint64_t bal, uint64_t dec, uint32_t n) {
+  if (bal >= (uint64_t)n * dec) return n;
+  return (uint32_t)tb_quot(bal, dec);
+}
+
 // Everything the round kernels need, passed by value as a kernel argument.
 struct DevSim {
   // shard and config
@@ -411,6 +459,7 @@ struct DevSim {
   uint64_t BW;
   UDiv64 bw_div;          // division by BW
   UDiv64 div_n, div_1000, div_ns;  // by n_all, 1000, n_servers (the synthetic apps' hashes, exact)
+  UDiv64 div_cq;          // by cq_pages (the free ring's index; re-made wherever cq_pages changes)
   SGN_GLB uint64_t* stamps;     // diagnostics (nullptr unless SGN_STAMPS is set)
   SGN_GLB uint64_t* rdbg;       // ... per-round timeline of the persistent kernel
   uint32_t n_ranks;

@@ -489,6 +489,7 @@ int sgn_snapshot_restore(sgn_ctx* ctx, const sgn_snapshot* snap) {
     S.cq_next = (decltype(S.cq_next))n_next;
     S.cq_free = (decltype(S.cq_free))n_free;
     S.cq_pages = Z.cq_pages;
+    S.div_cq.init(Z.cq_pages);
   }
   if (spill_re) {
     dev_free(ctx, (void*)S.spill, S.spill_cap * sizeof(EvRec));

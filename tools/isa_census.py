@@ -1,0 +1,174 @@
+#!/usr/bin/env python3
+"""Static instruction census of one kernel from the compiler's assembly listing.
+
+Where do a kernel's instructions come from? Compile the source for the device only, with the
+Makefile's flags plus line tables, and attribute every instruction to the source line of its
+innermost `.loc` (an inlined helper's own line, summed over its inlined copies):
+
+    python tools/isa_census.py --compile shadow-gen_amd/csrc/engine.hip -o engine.s
+    python tools/isa_census.py engine.s [--kernel MANGLED] [--top 20] [--json]
+
+Output: the kernel's totals (instructions by unit, SGPR spills, scalar loads, ...) and the
+largest source lines. `--per-copy` lists, for the chosen lines, the instructions of each
+inlined copy (one copy = one distinct inlining chain), which is what tells a 64-bit software
+division (~90+ instructions a copy) from a 32-bit one (~30).
+"""
+import argparse
+import collections
+import json
+import pathlib
+import re
+import subprocess
+import sys
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+TGEN_ROUNDS = "_ZN3sgn8k_roundsILj2ELb0EEEvPKNS_6DevSimEjjj"  # k_rounds<TGEN, false>: config C
+# the Makefile's CXXFLAGS (device side), plus line tables
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+         "-gline-tables-only", "--cuda-device-only", "-S"]
+
+_LOC = re.compile(r"^\s*\.loc\s+(\d+)\s+(\d+)\s+\d+(.*)$")
+_FILE = re.compile(r'^\s*\.file\s+(\d+)\s+"[^"]*"\s+"([^"]+)"')
+_FILE1 = re.compile(r'^\s*\.file\s+(\d+)\s+"([^"]+)"')
+_INSN = re.compile(r"^\s+([a-z][a-z0-9_]+)\b")
+_CHAIN = re.compile(r"@\[\s*(.*?)\s*\]\s*$")
+
+
+def compile_asm(src, out, hipcc="/opt/rocm/bin/hipcc"):
+    src = pathlib.Path(src).resolve()
+    subprocess.run([hipcc, *FLAGS, "-I", str(ROOT / "include"), "-I", str(src.parent), src.name,
+                    "-o", str(pathlib.Path(out).resolve())], check=True, cwd=src.parent,
+                   capture_output=True)
+
+
+def _unit(op):
+    if op.startswith("s_"):
+        return "SALU"
+    if op.startswith("v_"):
+        return "VALU"
+    if op.startswith("ds_"):
+        return "LDS"
+    if op.startswith(("global_", "flat_", "buffer_", "scratch_")):
+        return "VMEM"
+    return "other"
+
+
+def census(asm_path, kernel=TGEN_ROUNDS):
+    """{'totals': {...}, 'lines': {(file, line): n}, 'copies': {(file, line): {chain: n}},
+    'salu_lines': {(file, line): n}} for one kernel of an assembly listing."""
+    files = {}
+    totals = collections.Counter()
+    lines = collections.Counter()
+    salu = collections.Counter()
+    copies = collections.defaultdict(collections.Counter)
+    meta = {}
+    inside = False
+    cur = ("?", 0)
+    chain = ""
+    with open(asm_path, errors="replace") as f:
+        for ln in f:
+            m = _FILE.match(ln) or _FILE1.match(ln)
+            if m:
+                files[int(m.group(1))] = pathlib.Path(m.group(2)).name
+                continue
+            if not inside:
+                if ln.startswith(kernel + ":"):
+                    inside = True
+                elif ln.startswith("    .name:") and ln.split()[-1] == kernel:
+                    meta["_hit"] = True
+                elif ln.startswith("  - ."):
+                    if meta.get("_hit"):
+                        break
+                    meta = {}
+                else:
+                    m = re.match(r"\s+\.(sgpr_spill_count|vgpr_spill_count|vgpr_count|sgpr_count|"
+                                 r"private_segment_fixed_size|group_segment_fixed_size):\s+(\d+)", ln)
+                    if m:
+                        meta[m.group(1)] = int(m.group(2))
+                continue
+            if ln.startswith(".Lfunc_end"):
+                inside = False
+                continue
+            m = _LOC.match(ln)
+            if m:
+                cur = (files.get(int(m.group(1)), m.group(1)), int(m.group(2)))
+                c = _CHAIN.search(m.group(3))
+                chain = c.group(1) if c else ""
+                continue
+            m = _INSN.match(ln)
+            if not m or ln.lstrip().startswith((".", ";")):
+                continue
+            op = m.group(1)
+            totals["instructions"] += 1
+            totals[_unit(op)] += 1
+            lines[cur] += 1
+            copies[cur][chain] += 1
+            if op.startswith("s_"):
+                salu[cur] += 1
+            for key, pat in (("v_writelane", "v_writelane"), ("v_readlane", "v_readlane"), ("s_nop", "s_nop"),
+                             ("s_load_dword*", "s_load_dword"), ("v_mad_u64_u32", "v_mad_u64_u32"),
+                             ("v_rcp_*", "v_rcp_"), ("s_waitcnt", "s_waitcnt")):
+                if op.startswith(pat):
+                    totals[key] += 1
+    meta.pop("_hit", None)
+    for k, v in meta.items():
+        totals["." + k] = v
+    return {"totals": dict(totals), "lines": dict(lines), "copies": {k: dict(v) for k, v in copies.items()},
+            "salu_lines": dict(salu)}
+
+
+def source_line(path_by_name, key):
+    p = path_by_name.get(key[0])
+    if not p or key[1] == 0:
+        return "(compiler-made control flow and exec-mask glue)" if key[1] == 0 else ""
+    try:
+        return p.read_text(errors="replace").splitlines()[key[1] - 1].strip()[:70]
+    except (OSError, IndexError):
+        return ""
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("asm", nargs="?")
+    ap.add_argument("--compile", metavar="SRC", help="compile SRC (a .hip file) to the listing -o names, then stop")
+    ap.add_argument("-o", default="engine.s")
+    ap.add_argument("--kernel", default=TGEN_ROUNDS)
+    ap.add_argument("--top", type=int, default=20)
+    ap.add_argument("--per-copy", default="", help="comma-separated FILE:LINE list: instructions per inlined copy")
+    ap.add_argument("--json", action="store_true")
+    a = ap.parse_args()
+    if a.compile:
+        compile_asm(a.compile, a.o)
+        return 0
+    if not a.asm:
+        ap.error("an assembly listing, or --compile SRC")
+    c = census(a.asm, a.kernel)
+    if not c["totals"]:
+        print("kernel not found:", a.kernel, file=sys.stderr)
+        return 1
+    if a.json:
+        print(json.dumps({"totals": c["totals"],
+                          "lines": {f"{k[0]}:{k[1]}": v for k, v in c["lines"].items()}}))
+        return 0
+    srcs = {p.name: p for p in (ROOT / "shadow-gen_amd" / "csrc").glob("*.h*")}
+    srcs.update({p.name: p for p in (ROOT / "include").glob("*.h")})
+    t = c["totals"]
+    print("| measure | value |\n|---|---|")
+    for k in ("instructions", "VALU", "SALU", "LDS", "VMEM", "s_waitcnt", ".sgpr_spill_count", "v_writelane",
+              "v_readlane", "s_nop", "s_load_dword*", ".vgpr_count", "v_mad_u64_u32", "v_rcp_*"):
+        print(f"| {k} | {t.get(k, 0):,} |")
+    print("\n| line | what it is | instr. | SALU | copies |\n|---|---|---|---|---|")
+    for key, n in sorted(c["lines"].items(), key=lambda kv: -kv[1])[:a.top]:
+        print(f"| {key[0]}:{key[1]} | `{source_line(srcs, key)}` | {n:,} | {c['salu_lines'].get(key, 0):,} | "
+              f"{len(c['copies'][key])} |")
+    for spec in filter(None, a.per_copy.split(",")):
+        fn, _, ln = spec.rpartition(":")
+        key = (fn, int(ln))
+        print(f"\n{spec}: {c['lines'].get(key, 0)} instructions")
+        for ch, n in sorted(c["copies"].get(key, {}).items(), key=lambda kv: -kv[1]):
+            print(f"  {n:5d}  {ch or '(not inlined)'}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
