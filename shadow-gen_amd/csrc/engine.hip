@@ -262,8 +262,63 @@ __device__ __forceinline__ void cnt_add(SGN_GLB uint64_t* p, uint64_t v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ uint32_t bucket_of(const DevSim& S, uint64_t t) {
-  return (uint32_t)S.bw_div.div(t - SIM_START) & (S.NB - 1);
+// ---- DevSim as the round kernels see it ----
+// Device code reads a uniform DevSim field as SK(field), with S in scope: either the struct in
+// memory (const DevSim&: SK is plain S.field, a scalar load where it is used) or the lane table
+// (SimTab, sgn_internal.h: one v_readlane_b32 per dword). The functions of the event path take
+// S as a template parameter; k_rounds<TGEN, *> passes the table, every other kernel the struct.
+struct SimTab {
+  uint32_t r[KTAB_REGS];
+  const DevSim* g;  // the struct in memory (sk_mem: fields indexed per lane, the rare paths)
+};
+// Filled at kernel entry, before any divergent branch: lane i of register j holds dword
+// ktab_src(j, i). The empty asm pins each load where it is (a load sunk into a divergent branch
+// would leave inactive lanes' dwords unloaded) and makes the value opaque, so the compiler
+// cannot turn a readlane back into a scalar load.
+__device__ __forceinline__ SimTab ktab_fill(const DevSim* __restrict__ g) {
+  SimTab t;
+  t.g = g;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t* p = (const uint32_t*)g;
+#pragma unroll
+  for (uint32_t j = 0; j < KTAB_REGS; j++) {
+    uint32_t v = p[ktab_src(j, lane)];
+    asm volatile("" : "+v"(v));
+    t.r[j] = v;
+  }
+  return t;
+}
+template <class T, uint32_t OFF>
+__device__ __forceinline__ T ktab_get(const SimTab& t) {
+  static_assert(sizeof(T) % 4 == 0 && OFF % 4 == 0 && OFF + sizeof(T) <= sizeof(DevSim), "whole dwords of DevSim");
+  uint32_t w[sizeof(T) / 4];
+#pragma unroll
+  for (uint32_t k = 0; k < sizeof(T) / 4; k++)
+    w[k] = (uint32_t)__builtin_amdgcn_readlane((int)t.r[ktab_reg(OFF + 4 * k)], (int)ktab_lane(OFF + 4 * k));
+  T v;
+  __builtin_memcpy(&v, w, sizeof(T));
+  return v;
+}
+template <uint32_t OFF, class F>
+__device__ __forceinline__ decltype(auto) sk_read(const DevSim& s, F f) {
+  return f(s);  // (a reference to the member: the expression S.field itself)
+}
+template <uint32_t OFF, class F>
+__device__ __forceinline__ auto sk_read(const SimTab& t, F f) {
+  return ktab_get<std::remove_cv_t<std::remove_reference_t<decltype(f(*t.g))>>, OFF>(t);
+}
+__device__ __forceinline__ const DevSim& sk_mem(const DevSim& s) { return s; }
+__device__ __forceinline__ const DevSim& sk_mem(const SimTab& t) { return *t.g; }
+#define SK(f) sk_read<(uint32_t)offsetof(DevSim, f)>(S, [](const DevSim& d_) -> decltype(auto) { return (d_.f); })
+// element i (a constant) of an array field
+#define SKE(f, i) \
+  sk_read<(uint32_t)(offsetof(DevSim, f) + (i) * sizeof(DevSim::f[0]))>(S, [](const DevSim& d_) -> decltype(auto) { return (d_.f[i]); })
+template <uint32_t kApp>
+constexpr bool kKtab = kApp == SGN_TRAFFIC_TGEN;  // (PERIODIC: 249-251 VGPRs, no room for four more)
+
+template <class SV>
+__device__ __forceinline__ uint32_t bucket_of(const SV& S, uint64_t t) {
+  return (uint32_t)SK(bw_div).div(t - SIM_START) & (SK(NB) - 1);
 }
 
 // CoDel control law (router/codel_queue.rs:285-298)
@@ -453,13 +508,14 @@ constexpr bool kPairOff = false;
 // A run whose calendar slab is full goes to the spill area with its slab index (lossless; the
 // round edge holds and the host re-lays the calendar out before the run can be due). Only a
 // full spill area is an overflow.
-__device__ __forceinline__ void spill_run(const DevSim& S, OutboxHdr* ob, uint32_t idx, const EvRec& r) {
-  SGN_GLB Ctrl* C = S.ctrl;
+template <class SV>
+__device__ __forceinline__ void spill_run(const SV& S, OutboxHdr* ob, uint32_t idx, const EvRec& r) {
+  SGN_GLB Ctrl* C = SK(ctrl);
   const uint64_t i = __hip_atomic_fetch_add(&C->spill_n, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (ob) cnt_add(ob->spilled, 1);
-  if (i < S.spill_cap) {
-    st_dev_rec(S.spill + i, r);
-    st_dev(&S.spill_idx[i], idx);
+  if (i < SK(spill_cap)) {
+    st_dev_rec(SK(spill) + i, r);
+    st_dev(&SK(spill_idx)[i], idx);
   } else if ((atomicOr(&C->overflow, OVF_BUCKET) & OVF_BUCKET) == 0) {
     C->overflow_info = r.dst;
   }
@@ -467,13 +523,14 @@ __device__ __forceinline__ void spill_run(const DevSim& S, OutboxHdr* ob, uint32
 
 // A run at position pos >= CAP of slab idx: the slab's extension when it has room, else the
 // spill area (lossless either way).
-__device__ __forceinline__ void place_overflow(const DevSim& S, OutboxHdr* ob, uint32_t idx, uint32_t pos,
+template <class SV>
+__device__ __forceinline__ void place_overflow(const SV& S, OutboxHdr* ob, uint32_t idx, uint32_t pos,
                                                const EvRec& r) {
-  if (S.ext) {
-    const uint64_t x = S.ext[idx];
-    const uint32_t k = pos - S.CAP;
+  if (SK(ext)) {
+    const uint64_t x = SK(ext)[idx];
+    const uint32_t k = pos - SK(CAP);
     if (k < (uint32_t)(x >> 40)) {
-      st_dev_rec(S.ext_pool + (x & EXT_OFF_MASK) + k, r);
+      st_dev_rec(SK(ext_pool) + (x & EXT_OFF_MASK) + k, r);
       return;
     }
   }
@@ -560,9 +617,9 @@ struct BigLDS {
 // without it (its registers are fully used; a traced run executes round by round).
 // kApp: the traffic kind (SGN_TRAFFIC_*), fixed per instantiation so that each kernel
 // carries only its application's code (fewer registers, no dead branches).
-template <bool kTrace, uint32_t kApp>
+template <bool kTrace, uint32_t kApp, class SV = DevSim>
 struct HostExec {
-  const DevSim& S;
+  const SV& S;
   SGN_GLB Ctrl* C;
   uint32_t h, gid, my_ip, my_unode;
   uint64_t now, we;
@@ -607,17 +664,17 @@ struct HostExec {
   uint32_t wk[5];
 #endif
 
-  __device__ HostExec(const DevSim& s, uint32_t hh, uint64_t w, uint32_t bucket1, uint32_t ks,
+  __device__ HostExec(const SV& s, uint32_t hh, uint64_t w, uint32_t bucket1, uint32_t ks,
                       LaneLDS<kApp>* l, const uint16_t* bs, Outbox<kApp>* o, const BigLDS* b)
-      : S(s), C(s.ctrl), h(hh), now(0), we(w), b1(bucket1), keep_slab(ks), L(l), bslab(bs), ob(o), bg(b) {}
+      : S(s), C(SK(ctrl)), h(hh), now(0), we(w), b1(bucket1), keep_slab(ks), L(l), bslab(bs), ob(o), bg(b) {}
 
   // the host's state into registers (once per round, only for hosts with something due);
   // fresh = false: a reload after park() (the pending digest runs in LDS continue)
   __device__ __forceinline__ void load(bool fresh = true) {
-    R = S.hrec + h;
+    R = SK(hrec) + h;
     const HostRec& r = *R;
     if constexpr (kApp == SGN_TRAFFIC_PERIODIC) {
-      const HostConst& k = S.hconst[h];
+      const HostConst& k = SK(hconst)[h];
       gid = k.gid;
       my_ip = k.ip;
       my_unode = k.unode;
@@ -632,7 +689,7 @@ struct HostExec {
     }
     // the hot line
     if constexpr (kSoa<kApp>) {
-      const SGN_GLB u64x2* T = (const SGN_GLB u64x2*)S.htile + hot_idx(h, 0);
+      const SGN_GLB u64x2* T = (const SGN_GLB u64x2*)SK(htile) + hot_idx(h, 0);
       // (chunk 7 first: the flags decide the cold loads below; then the rest in order of use)
       const u64x2 c7 = T[448];
       fl = (uint32_t)c7.y;
@@ -746,11 +803,11 @@ struct HostExec {
   // a peer's slot id | used-node index << 32: from the 4-byte table when sim_init built one
   // (half the bytes of the 8-byte one: config D's 1 M-host table is 4 MB, about an XCD's L2)
   __device__ __forceinline__ uint64_t peer_info(uint32_t dst) const {
-    if (S.peer32) {
-      const uint32_t v = S.peer32[dst];
-      return (v & ((1u << S.peer_sb) - 1u)) | ((uint64_t)(v >> S.peer_sb) << 32);
+    if (SK(peer32)) {
+      const uint32_t v = SK(peer32)[dst];
+      return (v & ((1u << SK(peer_sb)) - 1u)) | ((uint64_t)(v >> SK(peer_sb)) << 32);
     }
-    return S.peer[dst];
+    return SK(peer)[dst];
   }
   __device__ __forceinline__ void prefetch_peer(uint32_t np) {
     pf_peer = np;
@@ -765,17 +822,17 @@ struct HostExec {
   // (u64 % is a long software routine on the GPU; the results are the same integers)
   __device__ __forceinline__ uint64_t mod_by(const UDiv64& d, uint64_t x, uint64_t n) const { return x - d.div(x) * n; }
   __device__ __forceinline__ bool periodic_dst(uint64_t k, uint32_t* peer, uint32_t* uip) const {
-    const uint64_t r = sgn_flow_hash(S.flow_seed, gid, k);
-    if ((uint32_t)mod_by(S.div_1000, r, 1000u) < S.unknown_permille) {
+    const uint64_t r = sgn_flow_hash(SK(flow_seed), gid, k);
+    if ((uint32_t)mod_by(SK(div_1000), r, 1000u) < SK(unknown_permille)) {
       *uip = SGN_UNKNOWN_IP_BASE + (uint32_t)((r >> 32) & 0xFFFFu);
       return false;
     }
-    *peer = (uint32_t)mod_by(S.div_n, r >> 16, S.n_all);
+    *peer = (uint32_t)mod_by(SK(div_n), r >> 16, SK(n_all));
     return true;
   }
   __device__ __forceinline__ void prefetch_route() {
     if (pf_peer == NO_HOST) return;
-    const RouteEnt re = S.route[(size_t)my_unode * S.U + (uint32_t)(pf_pi >> 32)];
+    const RouteEnt re = SK(route)[(size_t)my_unode * SK(U) + (uint32_t)(pf_pi >> 32)];
     lr().rc_dst = pf_peer;
     lr().rc_sid = (uint32_t)pf_pi;
     lr().rc_lat = re.lat;
@@ -813,7 +870,7 @@ struct HostExec {
                              F_CODEL_DN | F_CODEL_DROP)) ||
                       cq_nr || cq_len || cq_bytes || fq_len || fq_head;
     if constexpr (kSoa<kApp>) {
-      SGN_GLB u64x2* T = (SGN_GLB u64x2*)S.htile + hot_idx(h, 0);
+      SGN_GLB u64x2* T = (SGN_GLB u64x2*)SK(htile) + hot_idx(h, 0);
       const uint32_t f = (fl & ~(F_FH_DIRTY | F_COLD)) | (cold ? F_COLD : 0u);
       T[0] = u64x2{r0, r1};
       T[64] = u64x2{r2, r3};
@@ -859,12 +916,12 @@ struct HostExec {
     // value, no cold line); the other kinds in their cold lines
     if constexpr (kApp == SGN_TRAFFIC_PERIODIC) {
 #ifndef SGN_EXP_NOCNT  // (cost experiments only, build_exp.sh: the traffic of each per-host stream)
-      const size_t nH = S.nH;
-      if (c_sent) cnt_add(&S.n_cnt[N_SENT * nH + h], c_sent);
-      if (c_popped) cnt_add(&S.n_cnt[N_POPPED * nH + h], c_popped);
-      if (c_deliv) cnt_add(&S.n_cnt[N_DELIVERED * nH + h], c_deliv);
+      const size_t nH = SK(nH);
+      if (c_sent) cnt_add(&SK(n_cnt)[N_SENT * nH + h], c_sent);
+      if (c_popped) cnt_add(&SK(n_cnt)[N_POPPED * nH + h], c_popped);
+      if (c_deliv) cnt_add(&SK(n_cnt)[N_DELIVERED * nH + h], c_deliv);
       if (c_maxcodel)
-        (void)__hip_atomic_fetch_max(&S.maxq[h], c_maxcodel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_max(&SK(maxq)[h], c_maxcodel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
     } else {
       r.max_codel = c_maxcodel;
@@ -874,10 +931,10 @@ struct HostExec {
     }
 #ifndef SGN_EXP_NONEXT
     const uint64_t nl = next_local_time();
-    if (nl != old_next) S.nextloc[h] = nl;
+    if (nl != old_next) SK(nextloc)[h] = nl;
     if (kApp == SGN_TRAFFIC_PERIODIC) {
       const uint32_t p = next_peer();
-      if (p != old_peer) S.npeer[h] = p;
+      if (p != old_peer) SK(npeer)[h] = p;
     }
 #endif
     if (hd_valid) st_dev_cq(cq_head_slot(), L->hd);
@@ -931,13 +988,13 @@ struct HostExec {
     return (double)(rng_next() >> 11) * 0x1.0p-53;
   }
 
-  __device__ __forceinline__ bool tr() const { return kTrace && S.trace_on; }
+  __device__ __forceinline__ bool tr() const { return kTrace && SK(trace_on); }
   __device__ __forceinline__ void trace(uint32_t kind, uint32_t peer, uint32_t flags, uint64_t a, uint64_t b,
                         uint64_t c) {
     if (!tr()) return;
     const uint64_t seq = R->tseq++;
     uint64_t pos = atomicAdd((unsigned long long*)&C->trace_n, 1ULL);
-    if (pos >= S.trace_cap) {
+    if (pos >= SK(trace_cap)) {
       atomicOr(&C->overflow, OVF_TRACE);
       return;
     }
@@ -951,7 +1008,7 @@ struct HostExec {
     r.c = c;
     r.seq = seq;
     r.rng_pos = R->rng_pos;
-    S.trace[pos] = r;
+    SK(trace)[pos] = r;
   }
 
   __device__ __forceinline__ void overflow(uint32_t bit) {
@@ -962,7 +1019,7 @@ struct HostExec {
   __device__ __forceinline__ void drain_rec(uint32_t status, uint32_t src, uint32_t dst, uint64_t seid,
                             uint32_t payload, uint32_t tag) {
     const uint64_t pos = atomicAdd((unsigned long long*)&C->drain_n, 1ULL);
-    if (pos >= S.drain_cap) {
+    if (pos >= SK(drain_cap)) {
       overflow(OVF_DRAIN);
       return;
     }
@@ -976,7 +1033,7 @@ struct HostExec {
     r.status = status;
     r.payload_len = payload;
     r.tag = tag;
-    S.drain[pos] = r;
+    SK(drain)[pos] = r;
   }
   __device__ __forceinline__ bool external() const { return kApp == SGN_TRAFFIC_EXTERNAL; }
 
@@ -985,7 +1042,7 @@ struct HostExec {
   template <int SL>
   __device__ __forceinline__ void schedule(uint64_t t) {
     uint64_t e = eid++;
-    if (t >= S.end_time) return;
+    if (t >= SK(end_time)) return;
     if (SL == SLOT_RO) { st0 = t; se0 = e; }
     if (SL == SLOT_RI) { st1 = t; se1 = e; }
     if (SL == SLOT_APP) { st2 = t; se2 = e; }
@@ -1137,9 +1194,9 @@ struct HostExec {
   // ---- CoDel (router/codel_queue.rs) on a chain of pool pages ----
   // The queue's runs in order fill the head page from cq_head's offset, whole pages, and the
   // tail page (L->cq_tp) up to run cq_nr - 1; only the head and tail runs are ever touched.
-  __device__ __forceinline__ SGN_GLB CodelEnt* cq_head_slot() { return S.codel + cq_head; }
+  __device__ __forceinline__ SGN_GLB CodelEnt* cq_head_slot() { return SK(codel) + cq_head; }
   __device__ __forceinline__ SGN_GLB CodelEnt* cq_tail_slot() {
-    return S.codel + ((size_t)L->cq_tp * CQ_PAGE + ((cq_head + cq_nr - 1) & (CQ_PAGE - 1)));
+    return SK(codel) + ((size_t)L->cq_tp * CQ_PAGE + ((cq_head + cq_nr - 1) & (CQ_PAGE - 1)));
   }
   // a page from the pool: the free ring's next entry, if it was freed before this round
   // (the entries of the current round are still being written by other waves)
@@ -1148,7 +1205,7 @@ struct HostExec {
     const uint64_t i = __hip_atomic_fetch_add(&C->pg_alloc, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     cnt_add(ob->pg_allocd, 1);
     if (i >= ob->pg_avail) return NO_HOST;
-    const uint32_t pg = ld_dev(&S.cq_free[umod64(S.div_cq, i, S.cq_pages)]);
+    const uint32_t pg = ld_dev(&SK(cq_free)[umod64(SK(div_cq), i, SK(cq_pages))]);
 #ifdef SGN_DIAG
     DGT_WAIT();
     DGT_END(DGT_CQALLOC, ta);
@@ -1158,7 +1215,7 @@ struct HostExec {
   __device__ __forceinline__ void cq_free_page(uint32_t pg) {
     DGT_BEGIN(tf);
     const uint64_t j = __hip_atomic_fetch_add(&C->pg_tail, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    st_dev(&S.cq_free[umod64(S.div_cq, j, S.cq_pages)], pg);
+    st_dev(&SK(cq_free)[umod64(SK(div_cq), j, SK(cq_pages))], pg);
     cnt_add(ob->pg_freed, 1);
     DGT_END(DGT_CQFREE, tf);
   }
@@ -1173,7 +1230,7 @@ struct HostExec {
       cq_head++;
     } else {
       const uint32_t pg = cq_head / CQ_PAGE;
-      const uint32_t nx = ld_dev(&S.cq_next[pg]);  // (neighbouring links belong to other hosts)
+      const uint32_t nx = ld_dev(&SK(cq_next)[pg]);  // (neighbouring links belong to other hosts)
       cq_free_page(pg);
       cq_head = nx * CQ_PAGE;
     }
@@ -1202,7 +1259,7 @@ struct HostExec {
           overflow(OVF_CODEL);
           return;
         }
-        st_dev(&S.cq_next[L->cq_tp], np);
+        st_dev(&SK(cq_next)[L->cq_tp], np);
         L->cq_tp = np;
       }
       L->tl.enqueue_ts = now;
@@ -1326,15 +1383,15 @@ struct HostExec {
   // ---- synthetic socket send queue (interface qdisc source for relay_inet_out) ----
   __device__ __forceinline__ FifoEnt* fq_slot(uint32_t i) {
     uint32_t idx = fq_head + i;
-    if (idx >= S.fifo_cap) idx -= S.fifo_cap;
-    return S.fifo + (size_t)h * S.fifo_cap + idx;
+    if (idx >= SK(fifo_cap)) idx -= SK(fifo_cap);
+    return SK(fifo) + (size_t)h * SK(fifo_cap) + idx;
   }
   // dst NO_HOST: a datagram to `addr`, an address outside the simulation (the trace keeps
   // it in a side array, S.fifo_addr, for the capture record)
   __device__ __forceinline__ bool fifo_push(uint32_t dst, uint32_t payload, uint32_t last, uint32_t count,
                             uint32_t tag, uint32_t addr = 0) {
-    if (fq_len >= S.fifo_cap) return false;
-    if (tr() && dst == NO_HOST) S.fifo_addr[fq_slot(fq_len) - S.fifo] = addr;
+    if (fq_len >= SK(fifo_cap)) return false;
+    if (tr() && dst == NO_HOST) SK(fifo_addr)[fq_slot(fq_len) - SK(fifo)] = addr;
     FifoEnt e;
     e.dst = dst;
     e.pay = (payload & 0xFFFFu) | (last << 16);
@@ -1367,15 +1424,15 @@ struct HostExec {
 
   // ---- Dns::addr_to_host_id (network/dns.rs:174) ----
   __device__ __forceinline__ bool dns_lookup(uint32_t ip, uint32_t* host) const {
-    uint32_t i = (ip * 0x9E3779B1u) & S.dns_mask;
+    uint32_t i = (ip * 0x9E3779B1u) & SK(dns_mask);
     while (true) {
-      uint32_t k = S.dns_key[i];
+      uint32_t k = SK(dns_key)[i];
       if (k == ip) {
-        *host = S.dns_val[i];
+        *host = SK(dns_val)[i];
         return true;
       }
       if (k == 0) return false;
-      i = (i + 1) & S.dns_mask;
+      i = (i + 1) & SK(dns_mask);
     }
   }
 
@@ -1393,7 +1450,7 @@ struct HostExec {
       for (uint32_t k = 0; k < m; k++) drain_rec(SGN_DRAIN_DELIVERED, src, gid, e0 + k, payload, tag);
     if (kApp == SGN_TRAFFIC_TGEN && (fl & F_SERVER) && (tag & SGN_TAG_REQ)) {
       const uint32_t c = tag & 3u;  // the class picks one of three (scalar) sizes
-      const uint64_t size = c == 0 ? S.file_bytes[0] : (c == 1 ? S.file_bytes[1] : S.file_bytes[2]);
+      const uint64_t size = c == 0 ? SKE(file_bytes, 0) : (c == 1 ? SKE(file_bytes, 1) : SKE(file_bytes, 2));
       const uint64_t n = (size + SGN_TGEN_MSS - 1) / SGN_TGEN_MSS;
       if (n == 0) return;
       const uint32_t last = (uint32_t)(size - (n - 1) * SGN_TGEN_MSS);
@@ -1416,7 +1473,7 @@ struct HostExec {
   // ---- Relay::forward_until_blocked (network/relay/mod.rs:201-273) for relay_inet_in:
   //      the router's CoDel queue -> the interface (relay_inet_out uses forward_out) ----
   __device__ __forceinline__ bool forward_in(uint64_t* dur) {
-    const bool boot = now < S.boot_end;
+    const bool boot = now < SK(boot_end);
     set_relay_state<1>(RELAY_FORWARDING);
     while (true) {
       Pkt p;
@@ -1539,12 +1596,12 @@ struct HostExec {
   // IF_POP of the send queue's head entry (an unknown address from the trace's side array)
   __device__ __forceinline__ void trace_pop(uint32_t dst, uint32_t payload, uint32_t tag) {
     trace(SGN_TRACE_IF_POP, dst, 0, now, (uint64_t)payload | ((uint64_t)tag << 32),
-          dst == NO_HOST ? S.fifo_addr[fq_slot(0) - S.fifo] : 0);
+          dst == NO_HOST ? SK(fifo_addr)[fq_slot(0) - SK(fifo)] : 0);
   }
   __device__ __forceinline__ void send_batch_(uint32_t dst, uint32_t payload, uint32_t tag, uint32_t n, bool pop) {
-    if (n == 0 || now >= S.end_time) return;
+    if (n == 0 || now >= SK(end_time)) return;
     DG(DG_BATCH);
-    const bool boot = now < S.boot_end;
+    const bool boot = now < SK(boot_end);
     if (dst == NO_HOST) {  // resolve_ip_to_host_id failed: InetDropped (worker.rs:347-357)
       cnt_add(&R->n_unknown, n);
       dr_add_same<0>(now, 0xFFFFFFFFULL | (2ULL << 32), 0, n);
@@ -1575,7 +1632,7 @@ struct HostExec {
       // bit the same decision
       const uint64_t pi = peer_info(dst);
       dsid = (uint32_t)pi;
-      const RouteEnt re = S.route[(size_t)my_unode * S.U + (uint32_t)(pi >> 32)];
+      const RouteEnt re = SK(route)[(size_t)my_unode * SK(U) + (uint32_t)(pi >> 32)];
       delay = re.lat;
       T = re.T;
       DGT_WAIT();
@@ -1713,14 +1770,14 @@ struct HostExec {
     // sent packets have consecutive ids (drops take none): one event run record each
     // RUN_MAX packets
     const uint32_t nrec = (nsent + RUN_MAX - 1) / RUN_MAX;
-    if (S.dynamic) {  // Worker::update_lowest_used_latency (no return value: fire and forget)
+    if (SK(dynamic)) {  // Worker::update_lowest_used_latency (no return value: fire and forget)
       min_nr(&C->min_used, delay);
     }
     SGN_GLB EvRec* dstp;
     uint32_t cap;
     uint32_t pos;
     uint32_t sidx = 0;  // owned: the slab index (its spill tag)
-    const bool owned = dst - S.lo < S.nH;
+    const bool owned = dst - SK(lo) < SK(nH);
     if (owned) {
       if (deliver >= ob->hz) {  // past the calendar's horizon (sim_init sizes NB so it cannot be)
         overflow(OVF_HORIZON);
@@ -1728,16 +1785,16 @@ struct HostExec {
       }
       c_runs += nrec;
       const uint32_t b = bucket_of(S, deliver);
-      const uint32_t slab = b == b1 ? keep_slab : (S.NB <= LDS_BSLAB ? bslab[b] : ld_dev(&S.bucket_slab[b]));
-      const size_t idx = (size_t)slab * S.G + ((dsid - S.lo) >> S.gsh);
+      const uint32_t slab = b == b1 ? keep_slab : (SK(NB) <= LDS_BSLAB ? bslab[b] : ld_dev(&SK(bucket_slab)[b]));
+      const size_t idx = (size_t)slab * SK(G) + ((dsid - SK(lo)) >> SK(gsh));
       // the bucket's pending minimum: folded in the workgroup's LDS table when it has one
       // (flush_bmin publishes it before the round's arrival), else one device atomic per run
       // (compiled for PERIODIC traffic only — configs B and D, where every host sends every
       // round; the TGEN kernel of config C keeps its per-run atomic, uncontended there)
-      if (kAggBmin<kApp> && S.agg_bmin)
-        atomicMin(&ob->bmin[b == b1 ? S.NB : b], (uint32_t)(deliver - ob->bbase));
+      if (kAggBmin<kApp> && SK(agg_bmin))
+        atomicMin(&ob->bmin[b == b1 ? SK(NB) : b], (uint32_t)(deliver - ob->bbase));
       else
-        min_nr(b == b1 ? ob->keepmin : &S.bucket_min[b], deliver);
+        min_nr(b == b1 ? ob->keepmin : &SK(bucket_min)[b], deliver);
       if (nrec == 1) {
         const uint32_t k = atomicAdd(&ob->n, 1u);  // LDS
         if (k < kObox<kApp>) {
@@ -1753,17 +1810,17 @@ struct HostExec {
         }
       }
       DGT_BEGIN(tsl);
-      pos = atomicAdd(&S.slab_n[idx], nrec);
+      pos = atomicAdd(&SK(slab_n)[idx], nrec);
       DGT_WAIT();
       DGT_END(DGT_SLAB, tsl);
-      dstp = S.pool + idx * S.CAP;
-      cap = S.CAP;
+      dstp = SK(pool) + idx * SK(CAP);
+      cap = SK(CAP);
       sidx = (uint32_t)idx;
     } else {
-      uint32_t lo = 0, hi = S.n_ranks, lov = 0;  // (rank_lo[0] = 0)
+      uint32_t lo = 0, hi = SK(n_ranks), lov = 0;  // (rank_lo[0] = 0)
       while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
-        const uint32_t v = S.rank_lo[mid];
+        const uint32_t v = SK(rank_lo)[mid];
         if (v <= dst) {
           lo = mid;
           lov = v;
@@ -1778,20 +1835,20 @@ struct HostExec {
         // persistent rounds: the receiving host group's bin in the peer's inbox (its gather
         // reads it next round); a full bin sends the run to the peer's slot instead
         atomicAdd(&ob->xc[lo], nrec);  // LDS
-        const uint32_t gr = (dsid - lov) >> S.gsh;
-        pos = atomicAdd(&S.xbin_n[((size_t)ob->xbuf * S.n_ranks + lo) * S.xgx + gr], nrec);
-        if (pos + nrec <= S.xbk) {
+        const uint32_t gr = (dsid - lov) >> SK(gsh);
+        pos = atomicAdd(&SK(xbin_n)[((size_t)ob->xbuf * SK(n_ranks) + lo) * SK(xgx) + gr], nrec);
+        if (pos + nrec <= SK(xbk)) {
           binned = true;
-          dstp = S.xp[lo].bins[ob->xbuf] + (size_t)gr * S.xbk;
-          cap = S.xbk;
+          dstp = SK(xp)[lo].bins[ob->xbuf] + (size_t)gr * SK(xbk);
+          cap = SK(xbk);
         }
       }
       if (!binned) {
         pos = atomicAdd(&ob->xn[lo], nrec);
         // the peer's block: the RCCL transport's send block (after its message records), or the
         // peer's inbox slot for this shard and round parity (persistent rounds: peer-mapped memory)
-        dstp = S.xp[lo].runs[ob->xbuf];
-        cap = ob->xbuf == 2 ? S.xslot : S.xislot;
+        dstp = SK(xp)[lo].runs[ob->xbuf];
+        cap = ob->xbuf == 2 ? SK(xslot) : SK(xislot);
       }
     }
     for (uint32_t m = 0; m < nrec; m++) {
@@ -1804,7 +1861,7 @@ struct HostExec {
       r.pc = payload | (k << 16);
       r.tag = tag;
       if (pos + m < cap) {
-        if (owned || !S.xsys)
+        if (owned || !SK(xsys))
           st_dev_rec(dstp + pos + m, r);
         else  // (another GPU's inbox)
           st_sys_rec(dstp + pos + m, r);
@@ -1828,7 +1885,7 @@ struct HostExec {
   // after another (a train's per-packet loss draws are the serial part of a round).
   __device__ __forceinline__ void forward_out_step() {
     DGT_BEGIN(tf0);
-    const bool boot = now < S.boot_end;
+    const bool boot = now < SK(boot_end);
     uint64_t dur = 0;
     bool blocked = false;
     // the cached packet, or the head entry's run: one instance of the bucket and of the send
@@ -1849,7 +1906,7 @@ struct HostExec {
         // round-robin qdisc with other sockets waiting: one packet, then this socket goes to
         // the back (NetworkInterface::pop, interface.rs:216-256); otherwise the leading
         // datagrams of the train that share a payload size
-        rr = S.qdisc_rr && fq_len > 1;
+        rr = SK(qdisc_rr) && fq_len > 1;
         run = (e.count == 1 || rr) ? 1u : e.count - 1;
         payload = e.count == 1 ? (e.pay >> 16) : (e.pay & 0xFFFFu);
       }
@@ -1880,7 +1937,7 @@ struct HostExec {
       if (cached) {
         // not in the send queue
       } else if (consumed == e.count) {
-        fq_head = fq_head + 1 == S.fifo_cap ? 0 : fq_head + 1;
+        fq_head = fq_head + 1 == SK(fifo_cap) ? 0 : fq_head + 1;
         fq_len--;
         if (fq_len == 0) fq_head = 0;  // (an empty queue's head is 0: an idle host's default)
         fl &= ~F_FH_DIRTY;
@@ -1888,7 +1945,7 @@ struct HostExec {
         // the socket still has data: re-queued behind the others (same length)
         FifoEnt m = e;
         m.count = e.count - consumed;
-        fq_head = fq_head + 1 == S.fifo_cap ? 0 : fq_head + 1;
+        fq_head = fq_head + 1 == SK(fifo_cap) ? 0 : fq_head + 1;
         *fq_slot(fq_len - 1) = m;
         lr().fh_idx = NO_HOST;  // the cached head is stale
         fl &= ~F_FH_DIRTY;
@@ -1930,23 +1987,23 @@ struct HostExec {
       uint32_t peer = 0;
       // an address outside the simulation (10.255.0.0/16, never registered) is NO_HOST
       dst = periodic_dst(k, &peer, &uip) ? peer : NO_HOST;
-      payload = S.payload_len;
+      payload = SK(payload_len);
       tag = SGN_TAG_DATA;
-      next_delay = S.period;
+      next_delay = SK(period);
     } else {
       uint32_t si = 0, cls = 0;
       {  // sgn_tgen_fetch
-        const uint64_t r = sgn_flow_hash(S.flow_seed, gid, k);
-        si = (uint32_t)mod_by(S.div_ns, r >> 8, S.n_servers);
+        const uint64_t r = sgn_flow_hash(SK(flow_seed), gid, k);
+        si = (uint32_t)mod_by(SK(div_ns), r >> 8, SK(n_servers));
         cls = (uint32_t)((r >> 40) % 3u);
       }
       DGT_BEGIN(tsv);
-      dst = S.servers[si];
+      dst = SK(servers)[si];
       DGT_WAIT();
       DGT_END(DGT_SVLD, tsv);
-      payload = S.req_payload;
+      payload = SK(req_payload);
       tag = SGN_TAG_REQ | cls;
-      next_delay = sgn_tgen_think(S.flow_seed, gid, k, S.period, S.period_jitter);
+      next_delay = sgn_tgen_think(SK(flow_seed), gid, k, SK(period), SK(period_jitter));
     }
     if (fifo_push(dst, payload, payload, 1, tag, uip))
       relay_notify<0>();  // Host::notify_socket_has_packets (host.rs:969-983)
@@ -2145,10 +2202,11 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
 __host__ __device__ __forceinline__ uint64_t codel_pages_bound(uint64_t due, uint64_t hosts) {
   return (due + 15 * (due < hosts ? due : hosts) + 15) / 16;
 }
-__device__ __forceinline__ uint64_t codel_round_bound(const DevSim& S, uint64_t occ, uint64_t ws, uint64_t we) {
-  const uint32_t nbk = ((bucket_of(S, we - 1) - bucket_of(S, ws)) & (S.NB - 1)) + 1;
-  const uint64_t capb = (uint64_t)nbk * S.G * S.CAP + S.ext_total;
-  return codel_pages_bound(occ < capb ? occ : capb, S.nH);
+template <class SV>
+__device__ __forceinline__ uint64_t codel_round_bound(const SV& S, uint64_t occ, uint64_t ws, uint64_t we) {
+  const uint32_t nbk = ((bucket_of(S, we - 1) - bucket_of(S, ws)) & (SK(NB) - 1)) + 1;
+  const uint64_t capb = (uint64_t)nbk * SK(G) * SK(CAP) + SK(ext_total);
+  return codel_pages_bound(occ < capb ? occ : capb, SK(nH));
 }
 __device__ __forceinline__ uint64_t pages_free(uint64_t avail, uint64_t alloc) {
   return avail > alloc ? avail - alloc : 0;
@@ -2162,25 +2220,25 @@ __device__ __forceinline__ uint64_t pages_free(uint64_t avail, uint64_t alloc) {
 // them with the runs; k_import's last block reduces them on every shard).
 __device__ void finalize_fused(const DevSim& S, uint32_t lane, uint32_t nch, uint64_t ws,
                                uint64_t we, uint32_t ks, uint32_t slab_b1, int local = 0) {
-  SGN_GLB Ctrl* C = S.ctrl;
+  SGN_GLB Ctrl* C = SK(ctrl);
   const uint32_t b0 = bucket_of(S, ws), b1 = bucket_of(S, we - 1);
   // one round trip: every value to read (chunk minima, spare-slab minimum, bucket minima,
   // lowest used latency) is fetched at once; the buckets [b0, b1) are consumed and b1 is
   // replaced, so neither is read
   uint64_t kk = INVALID, wn = INVALID, m = INVALID, od = 0;
   for (uint32_t i = lane; i < nch; i += 64) {
-    const uint64_t a = __hip_atomic_exchange(&S.fin_keep[i], (unsigned long long)INVALID,
+    const uint64_t a = __hip_atomic_exchange(&SK(fin_keep)[i], (unsigned long long)INVALID,
                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint64_t b = __hip_atomic_exchange(&S.fin_next[i], (unsigned long long)INVALID,
+    const uint64_t b = __hip_atomic_exchange(&SK(fin_next)[i], (unsigned long long)INVALID,
                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    od += __hip_atomic_exchange(&S.fin_occ[i], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    od += __hip_atomic_exchange(&SK(fin_occ)[i], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     kk = a < kk ? a : kk;
     wn = b < wn ? b : wn;
   }
-  for (uint32_t b = lane; b < S.NB; b += 64) {
-    const bool consumed = ((b - b0) & (S.NB - 1)) < ((b1 - b0) & (S.NB - 1)) || b == b1;
+  for (uint32_t b = lane; b < SK(NB); b += 64) {
+    const bool consumed = ((b - b0) & (SK(NB) - 1)) < ((b1 - b0) & (SK(NB) - 1)) || b == b1;
     if (!consumed) {
-      const uint64_t bm = ld_dev(&S.bucket_min[b]);
+      const uint64_t bm = ld_dev(&SK(bucket_min)[b]);
       m = bm < m ? bm : m;
     }
   }
@@ -2196,15 +2254,15 @@ __device__ void finalize_fused(const DevSim& S, uint32_t lane, uint32_t nch, uin
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) od += shfl_xor64(od, off);
   // then the writes (the caller drains them before publishing the round edge)
-  for (uint32_t i = lane; i <= nch; i += 64) st_dev(&S.fin_cnt[i], 0u);
+  for (uint32_t i = lane; i <= nch; i += 64) st_dev(&SK(fin_cnt)[i], 0u);
   if (lane == 0) {
-    for (uint32_t b = b0; b != b1; b = (b + 1) & (S.NB - 1))
-      st_dev(&S.bucket_min[b], (uint64_t)INVALID);  // consumed
+    for (uint32_t b = b0; b != b1; b = (b + 1) & (SK(NB) - 1))
+      st_dev(&SK(bucket_min)[b], (uint64_t)INVALID);  // consumed
     // the spare slab set (survivors + this round's new runs for b1) becomes bucket b1
-    st_dev(&S.bucket_slab[b1], ks);
+    st_dev(&SK(bucket_slab)[b1], ks);
     st_dev(&C->keep_slab, slab_b1);
     const uint64_t nb1 = km < kk ? km : kk;
-    st_dev(&S.bucket_min[b1], nb1);
+    st_dev(&SK(bucket_min)[b1], nb1);
     // CoDel page pool: the pages freed this round become allocatable in the next
     const uint64_t fr = __hip_atomic_exchange(&C->pg_freed, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint64_t avail = ld_dev(&C->pg_avail) + fr;
@@ -2222,16 +2280,16 @@ __device__ void finalize_fused(const DevSim& S, uint32_t lane, uint32_t nch, uin
       // guard for the next window alike (k_import): free pages, calendar occupancy, runs
       // exported this round (a bound on what any shard receives), slab runs per bucket
       uint64_t xmax = 0, xsum = 0;
-      for (uint32_t p = 0; p < S.n_ranks; p++) {
-        const uint64_t cnt = p == S.rank ? 0 : ld_dev(&S.xout_n[p]);
+      for (uint32_t p = 0; p < SK(n_ranks); p++) {
+        const uint64_t cnt = p == SK(rank) ? 0 : ld_dev(&SK(xout_n)[p]);
         xmax = cnt > xmax ? cnt : xmax;
         xsum += cnt;
       }
-      for (uint32_t p = 0; p < S.n_ranks; p++) {
-        const uint64_t cnt = p == S.rank ? 0 : ld_dev(&S.xout_n[p]);
+      for (uint32_t p = 0; p < SK(n_ranks); p++) {
+        const uint64_t cnt = p == SK(rank) ? 0 : ld_dev(&SK(xout_n)[p]);
         // the message records of the peer's outgoing block (travel with the runs); this
         // shard's own in its incoming block, where k_import reads every shard's message
-        SGN_GLB uint64_t* o = (SGN_GLB uint64_t*)((p == S.rank ? S.xin : S.xout) + (size_t)p * (S.xslot + XHDR));
+        SGN_GLB uint64_t* o = (SGN_GLB uint64_t*)((p == SK(rank) ? SK(xin) : SK(xout)) + (size_t)p * (SK(xslot) + XHDR));
         st_dev(o, cnt);
         st_dev(o + 1, m);
         st_dev(o + 2, mu);
@@ -2239,19 +2297,19 @@ __device__ void finalize_fused(const DevSim& S, uint32_t lane, uint32_t nch, uin
         st_dev(o + 4, pfree);
         st_dev(o + 5, occ);
         st_dev(o + 6, xsum);
-        st_dev(o + 7, (uint64_t)S.G * S.CAP + S.ext_total);
+        st_dev(o + 7, (uint64_t)SK(G) * SK(CAP) + SK(ext_total));
       }
       return;
     }
     const uint64_t min_next = m == INVALID ? EMU_MAX : m;  // unwrap_or(MAX)
     st_dev(&C->last_min_next, min_next);
     // Runahead::get (runahead.rs:44-57)
-    uint64_t ra = (S.dynamic && mu != INVALID) ? mu : S.min_possible;
-    ra = ra > S.runahead_cfg ? ra : S.runahead_cfg;
+    uint64_t ra = (SK(dynamic) && mu != INVALID) ? mu : SK(min_possible);
+    ra = ra > SK(runahead_cfg) ? ra : SK(runahead_cfg);
     // Controller::manager_finished_current_round (controller.rs:88-112)
     uint64_t ne = min_next + ra;
     if (ne < min_next || ne > EMU_MAX) ne = EMU_MAX;
-    ne = ne < S.end_time ? ne : S.end_time;
+    ne = ne < SK(end_time) ? ne : SK(end_time);
     st_dev(&C->active, min_next < ne ? 1u : 0u);
     if (min_next < ne) {  // the next round's guards (hold before it runs)
       const uint64_t need = codel_round_bound(S, occ, min_next, ne);
@@ -2318,13 +2376,13 @@ struct ExecLDS {
 // arrival goes there, so its wait covers only what other workgroups read.
 // kXb (k_rounds_x): the group's inbox bins (the runs other shards sent it last round) are read in
 // the round trip of its first gather and taken into the calendar (see take_bins).
-template <bool kTrace, uint32_t kApp, bool kBig, bool kXb = false, bool kDiag = true, typename AtEnd>
-__device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t ws, uint64_t we, uint32_t ks,
+template <bool kTrace, uint32_t kApp, bool kBig, bool kXb = false, bool kDiag = true, typename AtEnd, class SV>
+__device__ __forceinline__ void exec_group(const SV& S, uint32_t g, uint64_t ws, uint64_t we, uint32_t ks,
                            const ExecLDS& X, uint64_t* kmin_out, uint64_t* next_out,
                            AtEnd&& at_end) {
-  SGN_GLB Ctrl* C = S.ctrl;
+  SGN_GLB Ctrl* C = SK(ctrl);
   // per-wave diagnostics (SGN_STAMPS): compiled out of the kernels launched without them
-  SGN_GLB uint64_t* const stamps = kDiag ? S.stamps : nullptr;
+  SGN_GLB uint64_t* const stamps = kDiag ? SK(stamps) : nullptr;
   EvRec* lev = X.lev;
   uint16_t* lb = X.lb;
   uint16_t* lc = X.lc;
@@ -2333,35 +2391,35 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
   LaneLDS<kApp>* lslot = (LaneLDS<kApp>*)X.lslot;
   uint16_t* lbs = X.lbs;
   const uint32_t lane = threadIdx.x;
-  const uint32_t gsz = 1u << S.gsh;
-  const uint32_t h = (g << S.gsh) + lane;  // local host index
-  const bool valid = lane < gsz && h < S.nH;
+  const uint32_t gsz = 1u << SK(gsh);
+  const uint32_t h = (g << SK(gsh)) + lane;  // local host index
+  const bool valid = lane < gsz && h < SK(nH);
   const uint32_t bs = bucket_of(S, ws), be = bucket_of(S, we - 1);
-  const uint32_t nbk = ((be + S.NB - bs) & (S.NB - 1)) + 1;  // buckets overlapping the window
-  const uint32_t gbase = S.lo + (g << S.gsh);  // HostId of lane 0
+  const uint32_t nbk = ((be + SK(NB) - bs) & (SK(NB) - 1)) + 1;  // buckets overlapping the window
+  const uint32_t gbase = SK(lo) + (g << SK(gsh));  // HostId of lane 0
   const uint64_t clk0 = stamps ? __builtin_amdgcn_s_memtime() : 0;
 #ifdef SGN_DIAG
   if (stamps && lane < 32) stamps[SGN_STAMP_WORDS * (size_t)g + 48 + lane] = 0;
   __syncthreads();
 #endif
   const uint64_t rt0 = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-  const size_t ik = (size_t)ks * S.G + g;
-  SGN_GLB EvRec* pk = S.pool + ik * S.CAP;
+  const size_t ik = (size_t)ks * SK(G) + g;
+  SGN_GLB EvRec* pk = SK(pool) + ik * SK(CAP);
 
   uint64_t lmin = INVALID;
   uint32_t np = NO_HOST;  // PERIODIC: the next datagram's peer (store() of the host's last round)
   if (valid) {
-    lmin = S.nextloc[h];
-    if (kApp == SGN_TRAFFIC_PERIODIC) np = S.npeer[h];
+    lmin = SK(nextloc)[h];
+    if (kApp == SGN_TRAFFIC_PERIODIC) np = SK(npeer)[h];
   }
   Outbox<kApp>* ob = static_cast<Outbox<kApp>*>(X.ob);
   if (lane == 0) {
     ob->n = 0;
     ob->xmin = INVALID;
-    ob->hz = SIM_START + (S.bw_div.div(ws - SIM_START) + S.NB) * S.BW;
+    ob->hz = SIM_START + (SK(bw_div).div(ws - SIM_START) + SK(NB)) * SK(BW);
   }
   __syncthreads();
-  HostExec<kTrace, kApp> ex(S, h, we, be, ks, lslot + lane, lbs, ob, kBig ? X.big : nullptr);
+  HostExec<kTrace, kApp, SV> ex(S, h, we, be, ks, lslot + lane, lbs, ob, kBig ? X.big : nullptr);
   bool loaded = false;
   uint32_t N_all = 0, sorted = 0;
   uint64_t kmin = INVALID;
@@ -2401,8 +2459,8 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
           ob->rec[k] = r;
           ob->idx[k] = (uint32_t)ik;
         } else {
-          const uint32_t base = atomicAdd(&S.slab_n[ik], 1u);
-          if (base < S.CAP)
+          const uint32_t base = atomicAdd(&SK(slab_n)[ik], 1u);
+          if (base < SK(CAP))
             st_dev_rec(pk + base, r);
           else
             place_overflow(S, ob, (uint32_t)ik, base, r);
@@ -2416,7 +2474,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
     for (uint32_t j0 = 0; j0 < n; j0 += 64) {
       const uint32_t j = j0 + lane;
       EvRec r = r0;
-      if ((j0 > 0 || lane >= S.gspec) && j < n) r = ld_dev_rec(pb + j);
+      if ((j0 > 0 || lane >= SK(gspec)) && j < n) r = ld_dev_rec(pb + j);
       const bool due = j < n && (!last || r.time < we);
       const bool keep = j < n && !due;
       const uint64_t dm = __ballot(due);
@@ -2430,16 +2488,16 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
   // the fill exceeds both) the spill area's entries tagged with this slab (f: per 64-run batch,
   // every lane; ok = the lane holds one of the slab's runs, si = its spill-area index or ~0)
   auto big_scan = [&](size_t ib, SGN_GLB const EvRec* pb, uint32_t nraw, auto&& f) {
-    const uint32_t np = min(nraw, S.CAP);
+    const uint32_t np = min(nraw, SK(CAP));
     for (uint32_t j0 = 0; j0 < np; j0 += 64) {
       const uint32_t j = j0 + lane;
       EvRec r{};
       if (j < np) r = ld_dev_rec(pb + j);
       f(r, j < np, ~0ULL);
     }
-    const uint64_t x = S.ext ? S.ext[ib] : 0ULL;
+    const uint64_t x = SK(ext) ? SK(ext)[ib] : 0ULL;
     const uint32_t ecap = (uint32_t)(x >> 40), ne = min(nraw - np, ecap);
-    SGN_GLB const EvRec* pe = S.ext_pool + (x & EXT_OFF_MASK);
+    SGN_GLB const EvRec* pe = SK(ext_pool) + (x & EXT_OFF_MASK);
     for (uint32_t j0 = 0; j0 < ne; j0 += 64) {
       const uint32_t j = j0 + lane;
       EvRec r{};
@@ -2447,19 +2505,19 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
       f(r, j < ne, ~0ULL);
     }
     if (nraw - np > ecap) {
-      const uint64_t ns = min(X.big->spill_imp, S.spill_cap);
+      const uint64_t ns = min(X.big->spill_imp, SK(spill_cap));
       for (uint64_t i0 = 0; i0 < ns; i0 += 64) {
         const uint64_t i = i0 + lane;
-        const bool mine = i < ns && ld_dev(&S.spill_idx[i]) == (uint32_t)ib;
+        const bool mine = i < ns && ld_dev(&SK(spill_idx)[i]) == (uint32_t)ib;
         EvRec r{};
-        if (mine) r = ld_dev_rec(S.spill + i);
+        if (mine) r = ld_dev_rec(SK(spill) + i);
         f(r, mine, i);
       }
     }
   };
   // big_scan over the key fields only (the radix select's passes)
   auto big_scan_keys = [&](size_t ib, SGN_GLB const EvRec* pb, uint32_t nraw, auto&& f) {
-    const uint32_t np = min(nraw, S.CAP);
+    const uint32_t np = min(nraw, SK(CAP));
     for (uint32_t j0 = 0; j0 < np; j0 += 64) {
       const uint32_t j = j0 + lane;
       uint64_t t = 0, e = 0;
@@ -2467,9 +2525,9 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
       if (j < np) ld_dev_key(pb + j, t, e, src);
       f(t, e, src, j < np);
     }
-    const uint64_t x = S.ext ? S.ext[ib] : 0ULL;
+    const uint64_t x = SK(ext) ? SK(ext)[ib] : 0ULL;
     const uint32_t ecap = (uint32_t)(x >> 40), ne = min(nraw - np, ecap);
-    SGN_GLB const EvRec* pe = S.ext_pool + (x & EXT_OFF_MASK);
+    SGN_GLB const EvRec* pe = SK(ext_pool) + (x & EXT_OFF_MASK);
     for (uint32_t j0 = 0; j0 < ne; j0 += 64) {
       const uint32_t j = j0 + lane;
       uint64_t t = 0, e = 0;
@@ -2478,13 +2536,13 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
       f(t, e, src, j < ne);
     }
     if (nraw - np > ecap) {
-      const uint64_t ns = min(X.big->spill_imp, S.spill_cap);
+      const uint64_t ns = min(X.big->spill_imp, SK(spill_cap));
       for (uint64_t i0 = 0; i0 < ns; i0 += 64) {
         const uint64_t i = i0 + lane;
-        const bool mine = i < ns && ld_dev(&S.spill_idx[i]) == (uint32_t)ib;
+        const bool mine = i < ns && ld_dev(&SK(spill_idx)[i]) == (uint32_t)ib;
         uint64_t t = 0, e = 0;
         uint32_t src = 0;
-        if (mine) ld_dev_key(S.spill + i, t, e, src);
+        if (mine) ld_dev_key(SK(spill) + i, t, e, src);
         f(t, e, src, mine);
       }
     }
@@ -2492,7 +2550,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
   // first pass: the later runs of the window's last bucket move to the spare slab set; the due
   // runs' count and time range go to the piece state
   auto big_prepare = [&](size_t ib, uint32_t nraw, bool last) {
-    SGN_GLB const EvRec* pb = S.pool + ib * S.CAP;
+    SGN_GLB const EvRec* pb = SK(pool) + ib * SK(CAP);
     uint64_t tmin = INVALID, tmax = 0;
     uint32_t nd = 0;
     big_scan(ib, pb, nraw, [&](const EvRec& r, bool ok, uint64_t) {
@@ -2529,11 +2587,11 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
     const size_t ib = uni64(B.ib);
     const uint32_t nraw = uni32(B.nraw);
     const bool last = uni32(B.pad) != 0;
-    SGN_GLB const EvRec* pb = S.pool + ib * S.CAP;
+    SGN_GLB const EvRec* pb = SK(pool) + ib * SK(CAP);
     const uint64_t tmin = uni64(B.tmin);
     const bool have = uni32(B.have_prev) != 0;
     const BigKey kp = {uni64(B.kp[0]), uni64(B.kp[1]), uni64(B.kp[2])};
-    const bool fin = uni32(B.ndue - B.done) <= S.CAP;
+    const bool fin = uni32(B.ndue - B.done) <= SK(CAP);
     auto in_s = [&](const EvRec& r, bool ok, BigKey& k) {
       k = big_key(r, tmin);
       return ok && (!last || r.time < we) && (!have || bk_less(kp, k));
@@ -2563,7 +2621,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
           const uint32_t y = __shfl_up(incl, off, 64);
           if ((int)lane >= off) incl += y;
         }
-        const uint32_t want = S.CAP - acc;
+        const uint32_t want = SK(CAP) - acc;
         const uint32_t c0 = incl - ls + h0, c1 = c0 + h1, c2 = c1 + h2, c3 = c2 + h3;
         // this lane's largest bin whose cumulative count is <= want (-1: none)
         int dl = -1;
@@ -2596,20 +2654,20 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
       BigKey k;
       const bool sel = in_s(r, ok, k) && !bk_less(kt, k);
       const uint64_t m = __ballot(sel);
-      if (sel && N + lanes_below(m) < S.CAP) lev[N + lanes_below(m)] = r;
+      if (sel && N + lanes_below(m) < SK(CAP)) lev[N + lanes_below(m)] = r;
       N += (uint32_t)__popcll(m);
     });
     bool bad = false;
-    if (N > S.CAP || (!fin && N == 0)) {  // (cannot happen: the select bounds every piece by
+    if (N > SK(CAP) || (!fin && N == 0)) {  // (cannot happen: the select bounds every piece by
       // CAP and takes at least one run) never silent, and the pieces end
       if (lane == 0 && (atomicOr(&C->overflow, OVF_SEG) & OVF_SEG) == 0) C->overflow_info = gbase;
-      N = min(N, S.CAP);
+      N = min(N, SK(CAP));
       bad = true;
     }
     if (fin || bad) {
       // runs taken from the spill area are tagged done (the re-layout must not file them again)
       big_scan(ib, pb, nraw, [&](const EvRec&, bool ok, uint64_t si) {
-        if (ok && si != ~0ULL) st_dev(&S.spill_idx[si], SPILL_DEAD);
+        if (ok && si != ~0ULL) st_dev(&SK(spill_idx)[si], SPILL_DEAD);
       });
     }
     __syncthreads();
@@ -2628,11 +2686,11 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
   };
   auto slab_done = [&](size_t ib, uint32_t n) {
     if (lane == 0) {
-      st_dev(&S.slab_n[ib], 0u);  // consumed (or moved); nobody appends to it this round
+      st_dev(&SK(slab_n)[ib], 0u);  // consumed (or moved); nobody appends to it this round
       if (n && X.wacc)
         wacc_max(&X.wacc[W_MAXFILL], n);
       else if (n)
-        __hip_atomic_fetch_max(&S.w_cnt[W_MAXFILL * S.G + g], (uint64_t)n, __ATOMIC_RELAXED,
+        __hip_atomic_fetch_max(&SK(w_cnt)[W_MAXFILL * SK(G) + g], (uint64_t)n, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);  // high-water mark, this wave's slot
     }
   };
@@ -2645,28 +2703,28 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
   // an empty entry) for the bin's next use two rounds later; the runs were counted in this
   // shard's occupancy at the round edge (XH_TOT).
   auto take_bins = [&](SGN_GLB EvRec* bp, EvRec r, uint32_t q, uint32_t e, bool on) -> bool {
-    const uint32_t E = 1u << (S.n_ranks <= 2 ? 5u : S.n_ranks <= 4 ? 4u : 3u);
+    const uint32_t E = 1u << (SK(n_ranks) <= 2 ? 5u : SK(n_ranks) <= 4 ? 4u : 3u);
     bool slow = false;
     bool more = on;
     for (uint32_t e0 = 0;;) {
       const bool ok = more && r.pc != 0;
       if (ok) {
         SGN_GLB uint64_t* pw = (SGN_GLB uint64_t*)(bp + e0) + 3;
-        if (S.xsys) st_sys(pw, 0ull); else st_dev(pw, (uint64_t)0);
+        if (SK(xsys)) st_sys(pw, 0ull); else st_dev(pw, (uint64_t)0);
         if (r.time >= ob->hz) {
           if ((atomicOr(&C->overflow, OVF_HORIZON) & OVF_HORIZON) == 0) C->overflow_info = r.dst;
         } else {
           const uint32_t b = bucket_of(S, r.time);
-          const size_t idx = (size_t)lbs[b] * S.G + g;
-          bool direct = ((b - bs) & (S.NB - 1)) < nbk;
+          const size_t idx = (size_t)lbs[b] * SK(G) + g;
+          bool direct = ((b - bs) & (SK(NB) - 1)) < nbk;
           slow |= direct;
           if (!direct) {
             // (the workgroup's LDS table of bucket minima where the kernel has one, as for sends:
             // config D's ~100 k imports a round per shard would queue on a few bucket words)
-            if (kAggBmin<kApp> && S.agg_bmin)
+            if (kAggBmin<kApp> && SK(agg_bmin))
               atomicMin(&ob->bmin[b], (uint32_t)(r.time - ob->bbase));
             else
-              min_nr(&S.bucket_min[b], r.time);
+              min_nr(&SK(bucket_min)[b], r.time);
             const uint32_t k = atomicAdd(&ob->n, 1u);  // LDS
             if (k < kObox<kApp>) {
               ob->rec[k] = r;
@@ -2676,9 +2734,9 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
             }
           }
           if (direct) {
-            const uint32_t pos = atomicAdd(&S.slab_n[idx], 1u);
-            if (pos < S.CAP)
-              st_dev_rec(S.pool + idx * S.CAP + pos, r);
+            const uint32_t pos = atomicAdd(&SK(slab_n)[idx], 1u);
+            if (pos < SK(CAP))
+              st_dev_rec(SK(pool) + idx * SK(CAP) + pos, r);
             else
               place_overflow(S, ob, (uint32_t)idx, pos, r);
           }
@@ -2686,21 +2744,21 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
       }
       const uint64_t m = __ballot(ok && e == E - 1);
       e0 += E;
-      if (!m || e0 >= S.xbk) break;
-      more = on && ((m >> (q * E + E - 1)) & 1ull) && e0 + e < S.xbk;
+      if (!m || e0 >= SK(xbk)) break;
+      more = on && ((m >> (q * E + E - 1)) & 1ull) && e0 + e < SK(xbk);
       r = EvRec{};
-      if (more) r = S.xsys ? ld_sys_rec(bp + e0) : ld_dev_rec(bp + e0);
+      if (more) r = SK(xsys) ? ld_sys_rec(bp + e0) : ld_dev_rec(bp + e0);
     }
     return __ballot(slow) != 0;
   };
   for (uint32_t bi = 0; bi < nbk; bi++) {
     const uint64_t c0 = stamps ? __builtin_amdgcn_s_memtime() : 0;
-    const uint32_t b = (bs + bi) & (S.NB - 1);
+    const uint32_t b = (bs + bi) & (SK(NB) - 1);
     bool last = bi == nbk - 1;
-    uint64_t sub_end = last ? we : SIM_START + (S.bw_div.div(ws - SIM_START) + bi + 1) * S.BW;
+    uint64_t sub_end = last ? we : SIM_START + (SK(bw_div).div(ws - SIM_START) + bi + 1) * SK(BW);
     // ---- 1. gather the group's runs of bucket b that are due (all but the last bucket's
     //      runs at >= we, which join this round's new runs for it in the spare slab) ----
-    const size_t ib = (size_t)uni32(S.NB <= LDS_BSLAB ? lbs[b] : ld_dev(&S.bucket_slab[b])) * S.G + g;
+    const size_t ib = (size_t)uni32(SK(NB) <= LDS_BSLAB ? lbs[b] : ld_dev(&SK(bucket_slab)[b])) * SK(G) + g;
     // the slab's fill and its first GATHER_SPEC records in ONE round trip: the records are
     // loaded before the fill is known (S.gspec <= CAP; slots past the fill are ignored) — nothing
     // appends to a bucket's slab while its window runs (new runs for the window's last
@@ -2713,29 +2771,29 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
     // (compiled into the PERIODIC kernel only: same-box A/B, config B +25 %, while C's TGEN
     // kernel — whose rounds are set by its servers' trains — measured 0.7 % slower with it)
     const bool pair = kApp == SGN_TRAFFIC_PERIODIC && bi == 0 && nbk == 2;
-    SGN_GLB const EvRec* pb = S.pool + ib * S.CAP;
+    SGN_GLB const EvRec* pb = SK(pool) + ib * SK(CAP);
     EvRec r0{}, r1{};
     size_t ib1 = 0;
     SGN_GLB const EvRec* pb1 = nullptr;
     if (pair) {
-      ib1 = (size_t)(S.NB <= LDS_BSLAB ? lbs[(b + 1) & (S.NB - 1)] : ld_dev(&S.bucket_slab[(b + 1) & (S.NB - 1)])) * S.G + g;
-      pb1 = S.pool + ib1 * S.CAP;
+      ib1 = (size_t)(SK(NB) <= LDS_BSLAB ? lbs[(b + 1) & (SK(NB) - 1)] : ld_dev(&SK(bucket_slab)[(b + 1) & (SK(NB) - 1)])) * SK(G) + g;
+      pb1 = SK(pool) + ib1 * SK(CAP);
     }
     // k_rounds_x: the first pass over the group's inbox bins, in the same round trip (lane =
     // sender x E + entry, E entries per sender and pass)
-    const bool bins = kXb && bi == 0 && S.xin_bins != nullptr;
-    const uint32_t bsh = S.n_ranks <= 2 ? 5u : S.n_ranks <= 4 ? 4u : 3u;
+    const bool bins = kXb && bi == 0 && SK(xin_bins) != nullptr;
+    const uint32_t bsh = SK(n_ranks) <= 2 ? 5u : SK(n_ranks) <= 4 ? 4u : 3u;
     const uint32_t bq = lane >> bsh, be_ = lane & ((1u << bsh) - 1);
-    const bool bon = bins && bq < S.n_ranks && bq != S.rank && be_ < S.xbk;
-    SGN_GLB EvRec* bp = bon ? S.xin_bins + (((size_t)(ob->xbuf ^ 1u) * S.n_ranks + bq) * S.G + g) * S.xbk + be_ : nullptr;
+    const bool bon = bins && bq < SK(n_ranks) && bq != SK(rank) && be_ < SK(xbk);
+    SGN_GLB EvRec* bp = bon ? SK(xin_bins) + (((size_t)(ob->xbuf ^ 1u) * SK(n_ranks) + bq) * SK(G) + g) * SK(xbk) + be_ : nullptr;
     EvRec br{};
-    if (bon) br = S.xsys ? ld_sys_rec(bp) : ld_dev_rec(bp);
-    if (lane < S.gspec) {
+    if (bon) br = SK(xsys) ? ld_sys_rec(bp) : ld_dev_rec(bp);
+    if (lane < SK(gspec)) {
       r0 = ld_dev_rec(pb + lane);
       if (pair) r1 = ld_dev_rec(pb1 + lane);
     }
-    uint32_t nraw_v = ld_dev(&S.slab_n[ib]);
-    uint32_t n1raw_v = pair ? ld_dev(&S.slab_n[ib1]) : 0u;
+    uint32_t nraw_v = ld_dev(&SK(slab_n)[ib]);
+    uint32_t n1raw_v = pair ? ld_dev(&SK(slab_n)[ib1]) : 0u;
     // PERIODIC traffic (configs B and D: most executed hosts have their app timer due): the
     // host record of a lane whose local event is due in the window loads in the same round trip
     // as the gather, and the app's next route is prefetched behind the sort
@@ -2750,12 +2808,12 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
       // first bucket's (and its pair's) loads again (spill-area entries included, big path)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (kBig && lane == 0) X.big->spill_imp = ld_dev(&C->spill_n);
-      if (lane < S.gspec) {
+      if (lane < SK(gspec)) {
         r0 = ld_dev_rec(pb + lane);
         if (pair) r1 = ld_dev_rec(pb1 + lane);
       }
-      nraw_v = ld_dev(&S.slab_n[ib]);
-      n1raw_v = pair ? ld_dev(&S.slab_n[ib1]) : 0u;
+      nraw_v = ld_dev(&SK(slab_n)[ib]);
+      n1raw_v = pair ? ld_dev(&SK(slab_n)[ib1]) : 0u;
     }
     // (scalar copies after the host record's loads are issued: a readfirstlane waits for its load)
     const uint32_t nraw = uni32(nraw_v), n1raw = uni32(n1raw_v);
@@ -2763,9 +2821,9 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
     // kernels without it (kBig false: no slab extension exists, so a run past CAP went to the
     // spill area and the round edge held for the re-layout before the slab could be due) never
     // see one; if one did, it is an overflow, not a silent truncation.
-    const bool big = kBig && nraw > S.CAP;
-    if (!kBig && nraw > S.CAP && lane == 0) atomicOr((unsigned int*)&C->overflow, OVF_BUCKET);
-    const uint32_t n = min(nraw, S.CAP);
+    const bool big = kBig && nraw > SK(CAP);
+    if (!kBig && nraw > SK(CAP) && lane == 0) atomicOr((unsigned int*)&C->overflow, OVF_BUCKET);
+    const uint32_t n = min(nraw, SK(CAP));
     uint32_t N = 0;
     if (!big) {
       lcnt[lane] = 0;
@@ -2773,7 +2831,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
       slab_done(ib, n);
       // (merged only while the pair fits one 64-run pass: config D's slabs hold ~64 runs each,
       // and merging them made its longer per-lane rank sorts cost more than the pass saved)
-      if (pair && n + n1raw <= min(S.CAP, 64u)) {
+      if (pair && n + n1raw <= min(SK(CAP), 64u)) {
         gather_slab(pb1, r1, n1raw, true, N);
         slab_done(ib1, n1raw);
         bi = 1;  // the second bucket is done: this is the window's last sub-window
@@ -2888,12 +2946,12 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
         const bool has = i < no;
         uint32_t idx = 0, pos = 0;
         if (has) idx = ob->idx[i];
-        if (has && !half) pos = atomicAdd(&S.slab_n[idx], 1u);
+        if (has && !half) pos = atomicAdd(&SK(slab_n)[idx], 1u);
         pos = __shfl(pos, (int)(lane & ~1u), 64);
         if (has) {
           const EvRec& r = ob->rec[i];
-          if (pos < S.CAP) {
-            SGN_GLB char* q = (SGN_GLB char*)(S.pool + (size_t)idx * S.CAP + pos) + 16 * half;
+          if (pos < SK(CAP)) {
+            SGN_GLB char* q = (SGN_GLB char*)(SK(pool) + (size_t)idx * SK(CAP) + pos) + 16 * half;
             if (half)
               st_wt16(q, (uint64_t)r.src | ((uint64_t)r.dst << 32), (uint64_t)r.pc | ((uint64_t)r.tag << 32));
             else
@@ -2906,9 +2964,9 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
     } else {
       for (uint32_t i = lane; i < no; i += 64) {
         const uint32_t idx = ob->idx[i];
-        const uint32_t pos = atomicAdd(&S.slab_n[idx], 1u);
-        if (pos < S.CAP)
-          st_dev_rec(S.pool + (size_t)idx * S.CAP + pos, ob->rec[i]);
+        const uint32_t pos = atomicAdd(&SK(slab_n)[idx], 1u);
+        if (pos < SK(CAP))
+          st_dev_rec(SK(pool) + (size_t)idx * SK(CAP) + pos, ob->rec[i]);
         else
           place_overflow(S, ob, idx, pos, ob->rec[i]);
       }
@@ -2996,14 +3054,14 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
     wacc_add(&X.wacc[W_BYTES], w_bytes);
     if (n_pieces) wacc_add(&X.wacc[W_BIG], n_pieces);
   } else if (lane == 0) {
-    const size_t G = S.G;
-    if (ex_mask) cnt_add(&S.w_cnt[W_EXEC * G + g], (uint64_t)__popcll(ex_mask));
-    if (N_all) cnt_add(&S.w_cnt[W_RUNS * G + g], N_all);
-    if (n_sorted) cnt_add(&S.w_cnt[W_SORTED * G + g], n_sorted);
-    if (w_loss) cnt_add(&S.w_cnt[W_LOSS * G + g], w_loss);
-    if (w_lev) cnt_add(&S.w_cnt[W_LOCAL_EV * G + g], w_lev);
-    if (w_bytes) cnt_add(&S.w_cnt[W_BYTES * G + g], w_bytes);
-    if (n_pieces) cnt_add(&S.w_cnt[W_BIG * G + g], n_pieces);
+    const size_t G = SK(G);
+    if (ex_mask) cnt_add(&SK(w_cnt)[W_EXEC * G + g], (uint64_t)__popcll(ex_mask));
+    if (N_all) cnt_add(&SK(w_cnt)[W_RUNS * G + g], N_all);
+    if (n_sorted) cnt_add(&SK(w_cnt)[W_SORTED * G + g], n_sorted);
+    if (w_loss) cnt_add(&SK(w_cnt)[W_LOSS * G + g], w_loss);
+    if (w_lev) cnt_add(&SK(w_cnt)[W_LOCAL_EV * G + g], w_lev);
+    if (w_bytes) cnt_add(&SK(w_cnt)[W_BYTES * G + g], w_bytes);
+    if (n_pieces) cnt_add(&SK(w_cnt)[W_BIG * G + g], n_pieces);
   }
 }
 
@@ -3016,9 +3074,9 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
   __shared__ BigLDS big_;                                                            \
   ExecLDS X;                                                                         \
   X.lev = (EvRec*)lds_dyn;                                                           \
-  X.lb = (uint16_t*)(X.lev + S.CAP);                                                 \
-  X.lc = X.lb + ((S.CAP + 3) & ~3u);                                                 \
-  X.bmin = S.agg_bmin ? (uint32_t*)(lds_dyn + exec_lds_runs_bytes(S.CAP)) : nullptr;  \
+  X.lb = (uint16_t*)(X.lev + SK(CAP));                                                 \
+  X.lc = X.lb + ((SK(CAP) + 3) & ~3u);                                                 \
+  X.bmin = SK(agg_bmin) ? (uint32_t*)(lds_dyn + exec_lds_runs_bytes(SK(CAP))) : nullptr;  \
   X.lcnt = lcnt_;                                                                    \
   X.lcur = lcur_;                                                                    \
   X.lslot = lslot_;                                                                  \
@@ -3029,7 +3087,7 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
   if (threadIdx.x == 0) {                                                            \
     ob_.bmin = X.bmin;                                                               \
     ob_.xc = nullptr;                                                                \
-    big_.spill_imp = ld_dev(&S.ctrl->spill_imp);                                     \
+    big_.spill_imp = ld_dev(&SK(ctrl)->spill_imp);                                     \
   }
 
 // The workgroup's LDS table of bucket minima (S.agg_bmin): its sends of the round fold their
@@ -3040,19 +3098,19 @@ __device__ __forceinline__ void exec_group(const DevSim& S, uint32_t g, uint64_t
 // Entries are u32 offsets from the round's window start (a delivery is below the calendar's
 // horizon, at most (NB + 1) bucket widths ahead; sim_init enables the table only when that
 // fits 32 bits).
-template <uint32_t kApp>
-__device__ __forceinline__ void init_bmin(const DevSim& S, const ExecLDS& X) {
+template <uint32_t kApp, class SV>
+__device__ __forceinline__ void init_bmin(const SV& S, const ExecLDS& X) {
   if (kAggBmin<kApp> && X.bmin)
-    for (uint32_t i = threadIdx.x; i <= S.NB; i += blockDim.x) X.bmin[i] = 0xFFFFFFFFu;
+    for (uint32_t i = threadIdx.x; i <= SK(NB); i += blockDim.x) X.bmin[i] = 0xFFFFFFFFu;
 }
-template <uint32_t kApp>
-__device__ __forceinline__ void flush_bmin(const DevSim& S, const ExecLDS& X) {
+template <uint32_t kApp, class SV>
+__device__ __forceinline__ void flush_bmin(const SV& S, const ExecLDS& X) {
   if (!kAggBmin<kApp> || !X.bmin) return;
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i <= S.NB; i += blockDim.x) {
+  for (uint32_t i = threadIdx.x; i <= SK(NB); i += blockDim.x) {
     const uint32_t v = X.bmin[i];
     if (v != 0xFFFFFFFFu) {
-      min_nr(i == S.NB ? X.ob->keepmin : &S.bucket_min[i], X.ob->bbase + v);
+      min_nr(i == SK(NB) ? X.ob->keepmin : &SK(bucket_min)[i], X.ob->bbase + v);
       X.bmin[i] = 0xFFFFFFFFu;
     }
   }
@@ -3068,19 +3126,19 @@ __device__ bool arrive(const DevSim& S, uint32_t w, uint32_t nw, uint64_t kmin, 
     const uint32_t ch = w >> 6;
     const uint32_t csz = min(64u, nw - (ch << 6));
     const uint32_t nch = (nw + 63) >> 6;
-    if (occd) cnt_add(&S.fin_occ[ch], occd);
+    if (occd) cnt_add(&SK(fin_occ)[ch], occd);
     if (kmin != INVALID)
-      __hip_atomic_fetch_min(&S.fin_keep[ch], (unsigned long long)kmin, __ATOMIC_RELAXED,
+      __hip_atomic_fetch_min(&SK(fin_keep)[ch], (unsigned long long)kmin, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
     if (m != INVALID)
-      __hip_atomic_fetch_min(&S.fin_next[ch], (unsigned long long)m, __ATOMIC_RELAXED,
+      __hip_atomic_fetch_min(&SK(fin_next)[ch], (unsigned long long)m, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every store/atomic of the round done
-    const uint32_t c = __hip_atomic_fetch_add(&S.fin_cnt[ch], 1u, __ATOMIC_RELAXED,
+    const uint32_t c = __hip_atomic_fetch_add(&SK(fin_cnt)[ch], 1u, __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_AGENT);
     if (c == csz - 1) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const uint32_t t = __hip_atomic_fetch_add(&S.fin_cnt[nch], 1u, __ATOMIC_RELAXED,
+      const uint32_t t = __hip_atomic_fetch_add(&SK(fin_cnt)[nch], 1u, __ATOMIC_RELAXED,
                                                 __HIP_MEMORY_SCOPE_AGENT);
       last = t == nch - 1 ? 1u : 0u;
     }
@@ -3097,13 +3155,13 @@ __global__ __launch_bounds__(64, 2) void k_execute(const DevSim* __restrict__ Sg
   // the simulation constants are read from device memory where they are used (a by-value
   // kernel argument would pin ~90 scalar registers for the whole kernel)
   const DevSim& S = *Sg;
-  SGN_GLB Ctrl* C = S.ctrl;
+  SGN_GLB Ctrl* C = SK(ctrl);
   if (!C->active || C->xspill || C->hold) return;  // a held round waits for the host
   SGN_EXEC_LDS(X)
   const uint64_t ws = C->ws, we = C->we;
   const uint32_t ks = C->keep_slab;
-  if (S.NB <= LDS_BSLAB)
-    for (uint32_t i = threadIdx.x; i < S.NB; i += 64) X.lbs[i] = (uint16_t)S.bucket_slab[i];
+  if (SK(NB) <= LDS_BSLAB)
+    for (uint32_t i = threadIdx.x; i < SK(NB); i += 64) X.lbs[i] = (uint16_t)SK(bucket_slab)[i];
   if (threadIdx.x == 0) {
     X.ob->keepmin = &C->keep_min;
     X.ob->bbase = C->ws;
@@ -3111,7 +3169,7 @@ __global__ __launch_bounds__(64, 2) void k_execute(const DevSim* __restrict__ Sg
     X.ob->pg_freed = &C->pg_freed;
     X.ob->pg_allocd = &C->rnd_alloc;
     X.ob->spilled = &C->rnd_spill;
-    X.ob->xn = S.xout_n;
+    X.ob->xn = SK(xout_n);
     X.ob->xbuf = 2;  // (the RCCL send blocks)
   }
   init_bmin<kApp>(S, X);
@@ -3126,7 +3184,7 @@ __global__ __launch_bounds__(64, 2) void k_execute(const DevSim* __restrict__ Sg
   const uint32_t b1 = bucket_of(S, we - 1);
   // single shard: the round edge; multi-shard: the local part of it (comm.cpp finishes it)
   finalize_fused(S, threadIdx.x, (gridDim.x + 63) >> 6, ws, we, ks,
-                 S.NB <= LDS_BSLAB ? X.lbs[b1] : ld_dev(&S.bucket_slab[b1]), S.fuse_finalize ? 0 : 1);
+                 SK(NB) <= LDS_BSLAB ? X.lbs[b1] : ld_dev(&SK(bucket_slab)[b1]), SK(fuse_finalize) ? 0 : 1);
 }
 
 // ---- persistent rounds: a decentralized round edge ----
@@ -3154,19 +3212,19 @@ template <uint32_t kApp> struct RbLayout {
 };
 constexpr uint32_t RB_CS_MAX = 32, RB_MS_MAX = 16, RB_OS_MAX = 16, RB_CB_MAX = (RB_CH + 1) * RB_CS_MAX;
 
-template <uint32_t kApp>
-__device__ __forceinline__ void rb_arrive(const DevSim& S, uint32_t p, uint32_t w, uint32_t nw, uint64_t kmin,
+template <uint32_t kApp, class SV>
+__device__ __forceinline__ void rb_arrive(const SV& S, uint32_t p, uint32_t w, uint32_t nw, uint64_t kmin,
                                           uint64_t m, uint64_t occd) {
   if (threadIdx.x != 0) return;
   const uint32_t ch = w >> 6;
   const uint32_t csz = min(64u, nw - (ch << 6));
   using Y = RbLayout<kApp>;
-  SGN_GLB uint64_t* mn = S.rb_min + ((size_t)p * RB_CH + ch) * Y::MS;
+  SGN_GLB uint64_t* mn = SK(rb_min) + ((size_t)p * RB_CH + ch) * Y::MS;
   if (kmin != INVALID) min_nr(mn, kmin);
   if (m != INVALID) min_nr(mn + 1, m);
-  if (occd) cnt_add(&S.rb_occ[((size_t)p * RB_CH + ch) * Y::OS], occd);
+  if (occd) cnt_add(&SK(rb_occ)[((size_t)p * RB_CH + ch) * Y::OS], occd);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this round's stores and atomics done
-  SGN_GLB uint32_t* cnt = S.rb_cnt + (size_t)p * Y::CB;
+  SGN_GLB uint32_t* cnt = SK(rb_cnt) + (size_t)p * Y::CB;
   const uint32_t c = __hip_atomic_fetch_add(&cnt[ch * Y::CS], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (c == csz - 1) (void)__hip_atomic_fetch_add(&cnt[RB_CH * Y::CS], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -3178,8 +3236,8 @@ struct RbEdge {
                                          // allocated / freed, runs spilled (buffer p: stable)
   uint32_t active;
 };
-template <uint32_t kApp>
-__device__ __forceinline__ RbEdge rb_edge(const DevSim& S, uint32_t p, uint32_t nch, uint64_t ws, uint64_t we) {
+template <uint32_t kApp, class SV>
+__device__ __forceinline__ RbEdge rb_edge(const SV& S, uint32_t p, uint32_t nch, uint64_t ws, uint64_t we) {
   using Y = RbLayout<kApp>;
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t b0 = bucket_of(S, ws), b1 = bucket_of(S, we - 1);
@@ -3189,33 +3247,33 @@ __device__ __forceinline__ RbEdge rb_edge(const DevSim& S, uint32_t p, uint32_t 
   // a range load a valid word of it and ignore it; the single words are loaded by every lane
   // (one request), so no broadcast follows.
   const uint32_t nc = nch ? nch : 1u;
-  SGN_GLB uint64_t* mn = S.rb_min + ((size_t)p * RB_CH + min(lane, nc - 1)) * Y::MS;
+  SGN_GLB uint64_t* mn = SK(rb_min) + ((size_t)p * RB_CH + min(lane, nc - 1)) * Y::MS;
   uint64_t kk = ld_dev(mn), wn = ld_dev(mn + 1);
-  uint64_t od = ld_dev(&S.rb_occ[((size_t)p * RB_CH + min(lane, nc - 1)) * Y::OS]);
-  const uint64_t km = ld_dev(&S.rb_keep[p]), mu = ld_dev(&S.ctrl->min_used);
-  const uint64_t na = ld_dev(&S.rb_occ[3 * RB_CH * RB_OS_MAX + p]), ns = ld_dev(&S.rb_occ[3 * RB_CH * RB_OS_MAX + 3 + p]);
-  const uint64_t nf = ld_dev(&S.rb_free[p]);
+  uint64_t od = ld_dev(&SK(rb_occ)[((size_t)p * RB_CH + min(lane, nc - 1)) * Y::OS]);
+  const uint64_t km = ld_dev(&SK(rb_keep)[p]), mu = ld_dev(&SK(ctrl)->min_used);
+  const uint64_t na = ld_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + p]), ns = ld_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + 3 + p]);
+  const uint64_t nf = ld_dev(&SK(rb_free)[p]);
   // the buckets to scan: synthetic traffic — every pending event is a delivery, so it lies in
   // [we, we + max_lat) (sends happen inside a window and arrive at most max_lat later,
   // worker.rs:386-390): only the buckets after b1 up to bucket_of(we + max_lat - 1) can hold
   // one (b1: nb1 below; C scans ~151 of its 256 buckets, B and D ~51). CPU-submitted datagrams
   // may be filed further ahead: every bucket the window has not consumed. (The persistent
   // kernels run with NB <= LDS_BSLAB = 256: at most four buckets per lane.)
-  const bool ext = S.tkind == SGN_TRAFFIC_EXTERNAL;
-  const uint32_t span = (b1 - b0) & (S.NB - 1);
-  const uint32_t nscan = ext ? S.NB - 1 - span
-                             : (uint32_t)min<uint64_t>(S.NB - 1 - span, S.bw_div.div(S.max_lat + S.BW - 1) + 1);
+  const bool ext = SK(tkind) == SGN_TRAFFIC_EXTERNAL;
+  const uint32_t span = (b1 - b0) & (SK(NB) - 1);
+  const uint32_t nscan = ext ? SK(NB) - 1 - span
+                             : (uint32_t)min<uint64_t>(SK(NB) - 1 - span, SK(bw_div).div(SK(max_lat) + SK(BW) - 1) + 1);
   uint64_t m = INVALID;
   if (nscan) {
     uint64_t bm[4];
 #pragma unroll
     for (uint32_t q = 0; q < 4; q++)
-      bm[q] = ld_dev(&S.bucket_min[(b1 + 1 + min(lane + 64 * q, nscan - 1)) & (S.NB - 1)]);
+      bm[q] = ld_dev(&SK(bucket_min)[(b1 + 1 + min(lane + 64 * q, nscan - 1)) & (SK(NB) - 1)]);
 #pragma unroll
     for (uint32_t q = 0; q < 4; q++)
       if (lane + 64 * q < nscan) m = bm[q] < m ? bm[q] : m;
     for (uint32_t k = lane + 256; k < nscan; k += 64) {  // (NB > 256: not on the persistent path)
-      const uint64_t v = ld_dev(&S.bucket_min[(b1 + 1 + k) & (S.NB - 1)]);
+      const uint64_t v = ld_dev(&SK(bucket_min)[(b1 + 1 + k) & (SK(NB) - 1)]);
       m = v < m ? v : m;
     }
   }
@@ -3239,11 +3297,11 @@ __device__ __forceinline__ RbEdge rb_edge(const DevSim& S, uint32_t p, uint32_t 
   m = wn < m ? wn : m;
   e.min_next = m == INVALID ? EMU_MAX : m;  // unwrap_or(MAX)
   // Runahead::get (runahead.rs:44-57)
-  uint64_t ra = (S.dynamic && mu != INVALID) ? mu : S.min_possible;
-  ra = ra > S.runahead_cfg ? ra : S.runahead_cfg;
+  uint64_t ra = (SK(dynamic) && mu != INVALID) ? mu : SK(min_possible);
+  ra = ra > SK(runahead_cfg) ? ra : SK(runahead_cfg);
   uint64_t ne = e.min_next + ra;
   if (ne < e.min_next || ne > EMU_MAX) ne = EMU_MAX;
-  ne = ne < S.end_time ? ne : S.end_time;
+  ne = ne < SK(end_time) ? ne : SK(end_time);
   e.active = e.min_next < ne ? 1u : 0u;
   e.ws = e.min_next;
   e.we = ne;
@@ -3251,15 +3309,16 @@ __device__ __forceinline__ RbEdge rb_edge(const DevSim& S, uint32_t p, uint32_t 
 }
 
 // Workgroup 0's bookkeeping of a finished round [ws, we) (lane-parallel plain stores).
-__device__ __forceinline__ void rb_bookkeep(const DevSim& S, uint64_t ws, uint64_t we, uint64_t nb1,
+template <class SV>
+__device__ __forceinline__ void rb_bookkeep(const SV& S, uint64_t ws, uint64_t we, uint64_t nb1,
                                             uint32_t new_keep) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t b0 = bucket_of(S, ws), b1 = bucket_of(S, we - 1);
-  const uint32_t nc = (b1 - b0) & (S.NB - 1);
-  for (uint32_t i = lane; i < nc; i += 64) st_dev(&S.bucket_min[(b0 + i) & (S.NB - 1)], (uint64_t)INVALID);
+  const uint32_t nc = (b1 - b0) & (SK(NB) - 1);
+  for (uint32_t i = lane; i < nc; i += 64) st_dev(&SK(bucket_min)[(b0 + i) & (SK(NB) - 1)], (uint64_t)INVALID);
   if (lane == 0) {
-    st_dev(&S.bucket_min[b1], nb1);
-    st_dev(&S.bucket_slab[b1], new_keep);
+    st_dev(&SK(bucket_min)[b1], nb1);
+    st_dev(&SK(bucket_slab)[b1], new_keep);
   }
 }
 
@@ -3276,30 +3335,30 @@ __device__ __forceinline__ void rb_bookkeep(const DevSim& S, uint64_t ws, uint64
 // bookkeeping workgroup BEFORE it counts itself into the residency census — every workgroup
 // waits for the whole census, so no arrival can reach the buffers first. Buffers 1 and 2 are
 // reset during rounds 0 and 1 as before.
-template <uint32_t kApp>
-__device__ __forceinline__ void rb_reset0(const DevSim& S, uint32_t nch) {
+template <uint32_t kApp, class SV>
+__device__ __forceinline__ void rb_reset0(const SV& S, uint32_t nch) {
   using Y = RbLayout<kApp>;
   for (uint32_t i = threadIdx.x; i < nch; i += 64) {
-    st_dev(&S.rb_min[(size_t)i * Y::MS], (uint64_t)INVALID);
-    st_dev(&S.rb_min[(size_t)i * Y::MS + 1], (uint64_t)INVALID);
-    st_dev(&S.rb_occ[(size_t)i * Y::OS], (uint64_t)0);
+    st_dev(&SK(rb_min)[(size_t)i * Y::MS], (uint64_t)INVALID);
+    st_dev(&SK(rb_min)[(size_t)i * Y::MS + 1], (uint64_t)INVALID);
+    st_dev(&SK(rb_occ)[(size_t)i * Y::OS], (uint64_t)0);
   }
   for (uint32_t i = threadIdx.x; i <= nch; i += 64) {
     const size_t o = (size_t)(i == nch ? RB_CH : i) * Y::CS;
-    st_dev(&S.rb_cnt[o], 0u);
-    if (S.rb2_cnt) st_dev(&S.rb2_cnt[o], 0u);
+    st_dev(&SK(rb_cnt)[o], 0u);
+    if (SK(rb2_cnt)) st_dev(&SK(rb2_cnt)[o], 0u);
   }
-  if (S.xout_n)
-    for (uint32_t i = threadIdx.x; i < S.n_ranks; i += 64) {
-      st_dev(&S.xout_n[i], 0u);
-      st_dev(&S.xout_n[3 * S.n_ranks + i], 0u);  // (k_rounds_x: the per-peer totals)
+  if (SK(xout_n))
+    for (uint32_t i = threadIdx.x; i < SK(n_ranks); i += 64) {
+      st_dev(&SK(xout_n)[i], 0u);
+      st_dev(&SK(xout_n)[3 * SK(n_ranks) + i], 0u);  // (k_rounds_x: the per-peer totals)
     }
   if (threadIdx.x == 0) {
-    st_dev(&S.rb_keep[0], (uint64_t)INVALID);
-    st_dev(&S.rb_free[0], (uint64_t)0);
-    st_dev(&S.rb_occ[3 * RB_CH * RB_OS_MAX], (uint64_t)0);
-    st_dev(&S.rb_occ[3 * RB_CH * RB_OS_MAX + 3], (uint64_t)0);
-    st_dev(&S.rb_cnt[3 * RB_CB_MAX], 0u);  // the idle-gap barrier's counter
+    st_dev(&SK(rb_keep)[0], (uint64_t)INVALID);
+    st_dev(&SK(rb_free)[0], (uint64_t)0);
+    st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX], (uint64_t)0);
+    st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + 3], (uint64_t)0);
+    st_dev(&SK(rb_cnt)[3 * RB_CB_MAX], 0u);  // the idle-gap barrier's counter
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -3310,8 +3369,8 @@ __device__ __forceinline__ void rb_reset0(const DevSim& S, uint32_t nch) {
 static_assert(sizeof(Ctrl) % 8 == 0, "the control block is copied as 8-byte words");
 constexpr uint32_t kMirrorWords = sizeof(Ctrl) / 8 + 2;  // the block, the epoch, the stale mark
 __device__ __forceinline__ void fail_timeout(const DevSim& S) {
-  atomicOr((unsigned int*)&S.ctrl->overflow, OVF_TIMEOUT);
-  if (S.ctrl_mirror) st_sys(&S.ctrl_mirror[kMirrorWords - 1], 1ull);
+  atomicOr((unsigned int*)&SK(ctrl)->overflow, OVF_TIMEOUT);
+  if (SK(ctrl_mirror)) st_sys(&SK(ctrl_mirror)[kMirrorWords - 1], 1ull);
 }
 
 // Residency census (thread 0 of each workgroup): the workgroup counts itself in and waits,
@@ -3343,11 +3402,21 @@ __device__ __forceinline__ uint32_t census(SGN_GLB Ctrl* C, uint32_t P, uint32_t
   return v & 3u;
 }
 
+template <bool kTab>
+__device__ __forceinline__ decltype(auto) sim_view(const DevSim* __restrict__ Sg) {
+  if constexpr (kTab)
+    return ktab_fill(Sg);
+  else
+    return (*Sg);
+}
+
 template <uint32_t kApp, bool kBig, bool kDiag>
 __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint32_t max_rounds, uint32_t epoch,
                                             uint32_t res_base) {
-  const DevSim& S = *Sg;
-  SGN_GLB Ctrl* C = S.ctrl;
+  // TGEN: the lane table, filled here under full EXEC (every workgroup is one whole wave), once
+  // per launch: the host writes the device's DevSim only between launches (sim_upload)
+  decltype(auto) S = sim_view<kKtab<kApp>>(Sg);
+  SGN_GLB Ctrl* C = SK(ctrl);
   SGN_EXEC_LDS(X)
   // PERIODIC (configs B, D): the per-wave statistics in LDS for the launch (B: ~70 % of the
   // PMC writes were their per-round atomics); TGEN keeps the per-round no-return adds (config
@@ -3365,12 +3434,12 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
   // Slots are ordered by graph node (sim_init), so an XCD's hosts cover an eighth of the nodes
   // and their sends read an eighth of the route table's rows (config D: 2 of 16 MB, L2-resident).
   // Any fixed bijection works: a group's records belong to its workgroup for the launch.
-  uint32_t gq0 = w, gq1 = S.G, gqs = P;
+  uint32_t gq0 = w, gq1 = SK(G), gqs = P;
   if constexpr (kApp == SGN_TRAFFIC_PERIODIC) {
     const uint32_t x = w & 7u, cx = (P - x + 7u) >> 3;  // this class's workgroups
     uint32_t before = 0;                                 // workgroups of the classes below x
     for (uint32_t y = 0; y < x; y++) before += (P - y + 7u) >> 3;
-    const uint32_t s0 = (uint32_t)((uint64_t)S.G * before / P), s1 = (uint32_t)((uint64_t)S.G * (before + cx) / P);
+    const uint32_t s0 = (uint32_t)((uint64_t)SK(G) * before / P), s1 = (uint32_t)((uint64_t)SK(G) * (before + cx) / P);
     gq0 = s0 + (w >> 3);
     gq1 = s1;
     gqs = cx;
@@ -3423,9 +3492,9 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
   }
   // (the launch's first round number is read back at its end: nothing else writes it, and a
   // register live across the whole launch spilled the PERIODIC big-slab kernel)
-  const bool lds_tab = S.NB <= LDS_BSLAB;
+  const bool lds_tab = SK(NB) <= LDS_BSLAB;
   if (lds_tab)
-    for (uint32_t i = threadIdx.x; i < S.NB; i += 64) X.lbs[i] = (uint16_t)ld_dev(&S.bucket_slab[i]);
+    for (uint32_t i = threadIdx.x; i < SK(NB); i += 64) X.lbs[i] = (uint16_t)ld_dev(&SK(bucket_slab)[i]);
   init_bmin<kApp>(S, X);
   __syncthreads();
   uint32_t r = 0;
@@ -3440,32 +3509,32 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
       // reset buffer (r + 1) % 3 for the next round
       const uint32_t q = (r + 1) % 3;
       for (uint32_t i = threadIdx.x; i < nch; i += 64) {
-        st_dev(&S.rb_min[((size_t)q * RB_CH + i) * RbLayout<kApp>::MS], (uint64_t)INVALID);
-        st_dev(&S.rb_min[((size_t)q * RB_CH + i) * RbLayout<kApp>::MS + 1], (uint64_t)INVALID);
-        st_dev(&S.rb_occ[((size_t)q * RB_CH + i) * RbLayout<kApp>::OS], (uint64_t)0);
+        st_dev(&SK(rb_min)[((size_t)q * RB_CH + i) * RbLayout<kApp>::MS], (uint64_t)INVALID);
+        st_dev(&SK(rb_min)[((size_t)q * RB_CH + i) * RbLayout<kApp>::MS + 1], (uint64_t)INVALID);
+        st_dev(&SK(rb_occ)[((size_t)q * RB_CH + i) * RbLayout<kApp>::OS], (uint64_t)0);
       }
       for (uint32_t i = threadIdx.x; i <= nch; i += 64)  // the grid's chunks, then the top counter
-        st_dev(&S.rb_cnt[(size_t)q * RbLayout<kApp>::CB + (i == nch ? RB_CH : i) * RbLayout<kApp>::CS], 0u);
+        st_dev(&SK(rb_cnt)[(size_t)q * RbLayout<kApp>::CB + (i == nch ? RB_CH : i) * RbLayout<kApp>::CS], 0u);
       if (threadIdx.x == 0) {
-        st_dev(&S.rb_keep[q], (uint64_t)INVALID);
-        st_dev(&S.rb_free[q], (uint64_t)0);
-        st_dev(&S.rb_occ[3 * RB_CH * RB_OS_MAX + q], (uint64_t)0);
-        st_dev(&S.rb_occ[3 * RB_CH * RB_OS_MAX + 3 + q], (uint64_t)0);
+        st_dev(&SK(rb_keep)[q], (uint64_t)INVALID);
+        st_dev(&SK(rb_free)[q], (uint64_t)0);
+        st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + q], (uint64_t)0);
+        st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + 3 + q], (uint64_t)0);
       }
     }
     // diagnostics (SGN_STAMPS): per round of this launch, {earliest start, latest arrival,
     // round edge known} on the 100 MHz clock
-    SGN_GLB uint64_t* rd = kDiag && S.rdbg ? S.rdbg + 3 * (size_t)(r & 127) : nullptr;
+    SGN_GLB uint64_t* rd = kDiag && SK(rdbg) ? SK(rdbg) + 3 * (size_t)(r & 127) : nullptr;
     if (rd && threadIdx.x == 0)
       __hip_atomic_fetch_min(rd, (unsigned long long)__builtin_amdgcn_s_memrealtime(),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x == 0) {
-      X.ob->keepmin = &S.rb_keep[p];
+      X.ob->keepmin = &SK(rb_keep)[p];
       X.ob->bbase = ws;
       X.ob->pg_avail = rs.pg_avail;
-      X.ob->pg_freed = &S.rb_free[p];
-      X.ob->pg_allocd = &S.rb_occ[3 * RB_CH * RB_OS_MAX + p];
-      X.ob->spilled = &S.rb_occ[3 * RB_CH * RB_OS_MAX + 3 + p];
+      X.ob->pg_freed = &SK(rb_free)[p];
+      X.ob->pg_allocd = &SK(rb_occ)[3 * RB_CH * RB_OS_MAX + p];
+      X.ob->spilled = &SK(rb_occ)[3 * RB_CH * RB_OS_MAX + 3 + p];
     }
     uint64_t kall = INVALID, mall = INVALID, oall = 0;
     bool arrived = false;
@@ -3491,7 +3560,7 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
     // grid barrier: every chunk complete, bounded
     uint32_t spins = 0;
     bool ok = true;
-    while (ld_dev(&S.rb_cnt[(size_t)p * RbLayout<kApp>::CB + RB_CH * RbLayout<kApp>::CS]) < nch) {
+    while (ld_dev(&SK(rb_cnt)[(size_t)p * RbLayout<kApp>::CB + RB_CH * RbLayout<kApp>::CS]) < nch) {
       // (TGEN: 1563 workgroups poll one word; a longer sleep between polls leaves the memory
       // side to the last arrivals' atomics: same-box A/B on C, 3639 -> 3586 us per 100-round
       // launch; PERIODIC: 8, see RbLayout)
@@ -3502,7 +3571,7 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
       }
     }
     if (!ok) {
-      if (threadIdx.x == 0) fail_timeout(S);
+      if (threadIdx.x == 0) fail_timeout(sk_mem(S));
       return;
     }
     asm volatile("" ::: "memory");
@@ -3514,19 +3583,19 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
     // round's bucket indices again once t >= bucketstart(ws) + NB * BW, and t < we' + max_lat.
     // Then (every workgroup decides alike) workgroup 0 does it now and a second grid barrier
     // keeps every send of the next round behind it (a lost bucket minimum).
-    const uint64_t span = (uint64_t)S.NB * S.BW;
-    const uint64_t bstart = SIM_START + S.bw_div.div(ws - SIM_START) * S.BW;
-    const bool gap = e.active && (e.we + S.max_lat >= bstart + span || e.we + S.max_lat < e.we);
+    const uint64_t span = (uint64_t)SK(NB) * SK(BW);
+    const uint64_t bstart = SIM_START + SK(bw_div).div(ws - SIM_START) * SK(BW);
+    const bool gap = e.active && (e.we + SK(max_lat) >= bstart + span || e.we + SK(max_lat) < e.we);
     if (gap) {
       if (w == wbk) rb_bookkeep(S, ws, we, e.nb1, ks);  // (the previous round's: done at this round's start)
       if (threadIdx.x == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // workgroup 0's stores are done
-        SGN_GLB uint32_t* gc = S.rb_cnt + 3 * RB_CB_MAX;
+        SGN_GLB uint32_t* gc = SK(rb_cnt) + 3 * RB_CB_MAX;
         const uint32_t target = (rs.ngap + 1) * P;
         __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         uint32_t sp = 0;
         while (ld_dev(gc) < target && ++sp < (1u << 24)) __builtin_amdgcn_s_sleep(2);
-        if (sp >= (1u << 24)) fail_timeout(S);
+        if (sp >= (1u << 24)) fail_timeout(sk_mem(S));
         rs.ngap++;
       }
     }
@@ -3534,7 +3603,7 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
     if (threadIdx.x == 0) {
       // the spare slab set (survivors + this round's new runs for b1) becomes bucket b1
       const uint32_t b1 = bucket_of(S, we - 1);
-      const uint32_t slab_b1 = lds_tab ? X.lbs[b1] : ld_dev(&S.bucket_slab[b1]);
+      const uint32_t slab_b1 = lds_tab ? X.lbs[b1] : ld_dev(&SK(bucket_slab)[b1]);
       if (lds_tab) X.lbs[b1] = (uint16_t)ks;
       rs.pend = gap ? 0u : 1u;
       rs.pend_ws = ws;
@@ -3569,9 +3638,9 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
   if (X.wacc && threadIdx.x < W_N && X.wacc[threadIdx.x] && gq0 < gq1) {
     const uint32_t k = threadIdx.x;
     if (k == W_MAXFILL)
-      __hip_atomic_fetch_max(&S.w_cnt[k * S.G + gq0], X.wacc[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_max(&SK(w_cnt)[k * SK(G) + gq0], X.wacc[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else
-      cnt_add(&S.w_cnt[k * S.G + gq0], X.wacc[k]);
+      cnt_add(&SK(w_cnt)[k * SK(G) + gq0], X.wacc[k]);
   }
   // the last round's bookkeeping and the host-visible control block
   if (w == wbk) {
@@ -3591,13 +3660,13 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
     }
     // ... and its copy in host memory: after the last barrier no other workgroup writes the
     // control block (their counters and flags arrived with them)
-    if (S.ctrl_mirror) {
+    if (SK(ctrl_mirror)) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       constexpr uint32_t NW = sizeof(Ctrl) / 8;
-      for (uint32_t i = threadIdx.x; i < NW; i += 64) st_sys(&S.ctrl_mirror[i], ld_dev(&((SGN_GLB uint64_t*)C)[i]));
+      for (uint32_t i = threadIdx.x; i < NW; i += 64) st_sys(&SK(ctrl_mirror)[i], ld_dev(&((SGN_GLB uint64_t*)C)[i]));
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (threadIdx.x == 0) st_sys(&S.ctrl_mirror[NW], (uint64_t)epoch);
+      if (threadIdx.x == 0) st_sys(&SK(ctrl_mirror)[NW], (uint64_t)epoch);
     }
   }
 }

@@ -511,6 +511,61 @@ struct DevSim {
   SGN_GLB uint64_t* htile;    // PERIODIC: the hot lines, tiled (hot_idx; null: in HostRec)
 };
 
+// ---- the lane table: DevSim in VGPR lanes for a launch (k_rounds<TGEN, *>) ----
+// The round kernel reads the launch-invariant DevSim fields wherever it uses them; read from
+// memory, each use is a scalar load that the wave's only instruction stream waits for (the
+// compiler reloads rather than keep ~200 dwords in scalar registers). The table holds the
+// struct's dwords in KTAB_REGS vector registers instead — dword d in lane d % 64 of register
+// d / 64, filled once at kernel entry under full EXEC — and a uniform field is one constant-lane
+// v_readlane_b32 per dword: no memory access, no wait. A field that straddles a 256-byte
+// boundary takes its dwords from two registers. tests/native/ktab_check.cpp checks the index
+// arithmetic against the struct on the host.
+constexpr uint32_t KTAB_DWORDS = (uint32_t)(sizeof(DevSim) / 4);
+constexpr uint32_t KTAB_REGS = (KTAB_DWORDS + 63) / 64;
+static_assert(sizeof(DevSim) % 4 == 0 && alignof(DevSim) >= 4, "the table is filled dword by dword");
+static_assert(KTAB_REGS <= 4, "DevSim outgrew four table registers (1024 bytes): the round kernel has no more to spare");
+// byte offset of a field's dword -> its register and lane
+__host__ __device__ constexpr uint32_t ktab_reg(uint32_t off) { return off >> 8; }
+__host__ __device__ constexpr uint32_t ktab_lane(uint32_t off) { return (off >> 2) & 63u; }
+// the dword that lane `lane` of register `reg` loads at the fill (the last register's lanes past
+// the struct's end load its last dword again: nothing is read beyond sizeof(DevSim))
+__host__ __device__ constexpr uint32_t ktab_src(uint32_t reg, uint32_t lane) {
+  return reg * 64 + lane < KTAB_DWORDS ? reg * 64 + lane : KTAB_DWORDS - 1;
+}
+// Host twin of the fill and of the accessor (the device forms are in engine.hip).
+struct KTabImage {
+  uint32_t r[KTAB_REGS][64];
+};
+inline void ktab_pack(const DevSim& s, KTabImage* t) {
+  const unsigned char* p = (const unsigned char*)&s;
+  for (uint32_t j = 0; j < KTAB_REGS; j++)
+    for (uint32_t i = 0; i < 64; i++) __builtin_memcpy(&t->r[j][i], p + 4 * (size_t)ktab_src(j, i), 4);
+}
+template <class T>
+inline T ktab_read(const KTabImage& t, uint32_t off) {
+  static_assert(sizeof(T) % 4 == 0, "fields are whole dwords");
+  uint32_t w[sizeof(T) / 4];
+  for (uint32_t k = 0; k < sizeof(T) / 4; k++) w[k] = t.r[ktab_reg(off + 4 * k)][ktab_lane(off + 4 * k)];
+  T v;
+  __builtin_memcpy(&v, w, sizeof(T));
+  return v;
+}
+// The fields the round kernels read through the table (SK(field) in engine.hip): every uniform
+// scalar, pointer and UDiv64 member of DevSim that device code names. file_bytes is indexed by a
+// per-lane value and is read element by element (SKE).
+#define SGN_KTAB_FIELDS(X)                                                                                    \
+  X(n_all) X(lo) X(nH) X(U) X(end_time) X(boot_end) X(runahead_cfg) X(min_possible) X(max_lat) X(dynamic)     \
+  X(fifo_cap) X(cq_pages) X(qdisc_rr) X(trace_on) X(tkind) X(payload_len) X(unknown_permille) X(req_payload)  \
+  X(n_servers) X(diag_mode) X(flow_seed) X(period) X(period_jitter) X(servers) X(rlat) X(rloss) X(unode)      \
+  X(ip) X(sid_of) X(peer) X(peer32) X(peer_sb) X(route) X(host_of) X(dns_key) X(dns_val) X(dns_mask)          \
+  X(hrec) X(hconst) X(n_cnt) X(maxq) X(nextloc) X(npeer) X(codel) X(cq_next) X(cq_free) X(rb_free) X(fifo)    \
+  X(fifo_addr) X(pool) X(slab_n) X(bucket_slab) X(bucket_min) X(spill) X(spill_idx) X(spill_cap) X(ext)       \
+  X(ext_pool) X(ext_total) X(NB) X(G) X(CAP) X(gsh) X(w_cnt) X(fin_cnt) X(fin_keep) X(fin_next) X(fin_occ)    \
+  X(rb_min) X(rb_keep) X(rb_cnt) X(rb_occ) X(gspec) X(fuse_finalize) X(agg_bmin) X(BW) X(bw_div) X(div_n)     \
+  X(div_1000) X(div_ns) X(div_cq) X(stamps) X(rdbg) X(n_ranks) X(ctrl) X(trace) X(trace_cap) X(drain)         \
+  X(drain_cap) X(xout) X(xout_n) X(xin) X(xslot) X(rank) X(rank_lo) X(xp) X(xin_hdr) X(xin_runs) X(xin_cen)   \
+  X(rb2_cnt) X(xislot) X(xsys) X(xown) X(xbk) X(xin_bins) X(xbin_n) X(xgx) X(rdbg_wg) X(ctrl_mirror) X(htile)
+
 // Persistent multi-shard rounds (k_rounds_x): every shard owns an INBOX — per sender shard and
 // round parity a message (the round edge's, below) and a slot of xislot runs — that the senders
 // write directly (peer-mapped memory

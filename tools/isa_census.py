@@ -12,6 +12,13 @@ Output: the kernel's totals (instructions by unit, SGPR spills, scalar loads, ..
 largest source lines. `--per-copy` lists, for the chosen lines, the instructions of each
 inlined copy (one copy = one distinct inlining chain), which is what tells a 64-bit software
 division (~90+ instructions a copy) from a 32-bit one (~30).
+
+`--smem` lists every scalar load of the kernel instead: its source line and inlining chain, its
+base register and offset, and how many instructions later the first `s_waitcnt lgkmcnt(..)`
+follows in the listing (a load waited for at once stalls the wave's only instruction stream for
+a scalar-cache round trip), with a summary per base register:
+
+    python tools/isa_census.py engine.s --smem [--kernel MANGLED] [--json]
 """
 import argparse
 import collections
@@ -117,6 +124,79 @@ def census(asm_path, kernel=TGEN_ROUNDS):
             "salu_lines": dict(salu)}
 
 
+_SLOAD = re.compile(r"^\s+(s_(?:buffer_)?load_dword\w*)\s+([^,]+),\s*([^,]+),\s*(\S+)")
+_CHAIN_ENT = re.compile(r"([^\s@\[\]]+):(\d+):\d+")
+
+
+def smem(asm_path, kernel=TGEN_ROUNDS):
+    """Every scalar load of one kernel, in listing order: [{'op', 'dst', 'base', 'offset', 'file',
+    'line', 'chain': [(file, line), ...] (the inlining call sites, innermost first), 'wait': the
+    instructions from the load to the next s_waitcnt that names lgkmcnt (1: the very next one;
+    None: none before the function ends)}]. The distance follows the listing, not the branches."""
+    files = {}
+    out, pending = [], []
+    inside = False
+    cur, chain = ("?", 0), []
+    with open(asm_path, errors="replace") as f:
+        for ln in f:
+            m = _FILE.match(ln) or _FILE1.match(ln)
+            if m:
+                files[int(m.group(1))] = pathlib.Path(m.group(2)).name
+                continue
+            if not inside:
+                inside = ln.startswith(kernel + ":")
+                continue
+            if ln.startswith(".Lfunc_end"):
+                break
+            m = _LOC.match(ln)
+            if m:
+                cur = (files.get(int(m.group(1)), m.group(1)), int(m.group(2)))
+                c = _CHAIN.search(m.group(3))
+                chain = [(pathlib.Path(a).name, int(b)) for a, b in _CHAIN_ENT.findall(c.group(1))] if c else []
+                continue
+            m = _INSN.match(ln)
+            if not m or ln.lstrip().startswith((".", ";")):
+                continue
+            for p in pending:
+                p["wait"] += 1
+            if m.group(1) == "s_waitcnt" and "lgkmcnt" in ln:
+                pending = []
+            elif m.group(1) == "s_waitcnt" and re.match(r"\s+s_waitcnt\s+(0x[0-9a-f]+|\d+)\s*$", ln):
+                pending = []  # (a raw immediate: counted as a wait for everything)
+            s = _SLOAD.match(ln)
+            if s:
+                e = {"op": s.group(1), "dst": s.group(2).strip(), "base": s.group(3).strip(),
+                     "offset": s.group(4).strip(), "file": cur[0], "line": cur[1], "chain": list(chain), "wait": 0}
+                out.append(e)
+                pending.append(e)
+    for p in pending:
+        p["wait"] = None
+    return out
+
+
+def smem_report(loads, srcs):
+    t = collections.Counter()
+    by_base = collections.defaultdict(set)
+    for e in loads:
+        by_base[e["base"]].add(e["offset"])
+        t["loads"] += 1
+        if e["wait"] is not None and e["wait"] <= 5:
+            t["waited for within 5 instructions"] += 1
+        if e["wait"] == 1:
+            t["waited for by the next instruction"] += 1
+    print("| measure | value |\n|---|---|")
+    for k in ("loads", "waited for within 5 instructions", "waited for by the next instruction"):
+        print(f"| {k} | {t.get(k, 0)} |")
+    print("\n| base | loads | distinct offsets |\n|---|---|---|")
+    for b, offs in sorted(by_base.items(), key=lambda kv: -len(kv[1])):
+        print(f"| {b} | {sum(1 for e in loads if e['base'] == b)} | {len(offs)} |")
+    print("\n| line | what it is | inlined into | op | base | offset | next wait |\n|---|---|---|---|---|---|---|")
+    for e in loads:
+        ch = " < ".join(f"{a}:{b}" for a, b in e["chain"]) or "-"
+        print(f"| {e['file']}:{e['line']} | `{source_line(srcs, (e['file'], e['line']))}` | {ch} | {e['op']} | "
+              f"{e['base']} | {e['offset']} | {e['wait'] if e['wait'] is not None else '-'} |")
+
+
 def source_line(path_by_name, key):
     p = path_by_name.get(key[0])
     if not p or key[1] == 0:
@@ -136,12 +216,22 @@ def main():
     ap.add_argument("--top", type=int, default=20)
     ap.add_argument("--per-copy", default="", help="comma-separated FILE:LINE list: instructions per inlined copy")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--smem", action="store_true", help="list the kernel's scalar loads instead of the census")
     a = ap.parse_args()
     if a.compile:
         compile_asm(a.compile, a.o)
         return 0
     if not a.asm:
         ap.error("an assembly listing, or --compile SRC")
+    if a.smem:
+        loads = smem(a.asm, a.kernel)
+        if a.json:
+            print(json.dumps(loads))
+            return 0
+        srcs = {p.name: p for p in (ROOT / "shadow-gen_amd" / "csrc").glob("*.h*")}
+        srcs.update({p.name: p for p in (ROOT / "include").glob("*.h")})
+        smem_report(loads, srcs)
+        return 0
     c = census(a.asm, a.kernel)
     if not c["totals"]:
         print("kernel not found:", a.kernel, file=sys.stderr)
