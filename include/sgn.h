@@ -246,8 +246,9 @@ int sgn_run(sgn_ctx* ctx, uint64_t max_rounds, uint64_t* rounds_done);
  * buffers plus a few host counters and the engine is bit-deterministic, so a snapshot is exact:
  *   n  = sgn_run(ctx, 1, ..)                 s  = sgn_hosts_next_event_time
  *   cN = sgn_run_until(ctx, now + N, ..)     rN = sgn_snapshot_restore(first) + sgn_run_until(N)
- * All of it is single-shard: a context created with shard_count > 1 or joined to a local shard
- * group gets SGN_ESTATE (a multi-shard snapshot or pause needs a collective; not provided). */
+ * These calls are single-shard: a context created with shard_count > 1 or joined to a local
+ * shard group gets SGN_ESTATE from them, because a multi-shard snapshot or pause needs a
+ * collective over every shard at one round edge — the sgn_shards_* calls below. */
 
 /* Runs whole windows until the next window would start at or after t_emulated (EmulatedTime,
  * i.e. SGN_SIMULATION_START + simulated ns), or the simulation ends — the fork's rule "pause
@@ -300,6 +301,40 @@ typedef struct sgn_snapshot_info {
   double pack_ms;                            /* ... of which the calendar's scan + pack kernels */
 } sgn_snapshot_info;
 int sgn_snapshot_info_get(const sgn_snapshot* snap, sgn_snapshot_info* out);
+
+/* ---- run-control for sharded simulations ----
+ * ctxs: THIS process's shards — all n contexts of a local group (rank order), or the one context
+ * of a rank that has a communicator (n = 1). In the second form every rank makes the same call
+ * with the same arguments at the same round edge: a collective. Anything else (a part of a
+ * group, an unsharded context) is SGN_ESTATE; a null pointer is SGN_EINVAL.
+ *   n  = sgn_run / sgn_run_local_group(.., 1, ..)     cN = sgn_shards_run_until(now + N)
+ *   r  = sgn_shards_snapshot_restore(first)           rN = r + sgn_shards_run_until(N)
+ *
+ * sgn_shards_run_until follows sgn_run_until's rule exactly: every shard pauses at the first
+ * round edge whose next window starts at or after t_emulated (the multi-shard round edges compute
+ * that window from the same N messages on every shard, so all shards pause at the same edge, on
+ * the device); a target at or below the current window start, or an ended simulation, runs
+ * nothing. rounds_done (may be NULL): the rounds every shard ran. Ranks that pass different
+ * targets all get SGN_EINVAL before anything is launched. */
+int sgn_shards_run_until(sgn_ctx* const* ctxs, uint32_t n, uint64_t t_emulated, uint64_t* rounds_done);
+
+/* One snapshot per shard, all of the same resolved round edge (a round still held — a pool, a
+ * re-layout, runs waiting for a larger inbox — is resolved across the shards first). out[i] is
+ * owned by ctxs[i]; sgn_snapshot_free and sgn_snapshot_info_get apply to it. All or nothing: on
+ * any failure every snapshot taken in the call is freed and out[] is all NULL. */
+int sgn_shards_snapshot_save(sgn_ctx* const* ctxs, uint32_t n, sgn_snapshot** out /* [n] */);
+
+/* Every shard back to snaps[i], as sgn_snapshot_restore does for one: the shard's own state and
+ * pools (slab capacity, extensions, CoDel pages, spill area) return to the saved sizes. The one
+ * deliberate difference is the exchange layer, which belongs to the sequence of launches: inboxes
+ * and exchange slots keep the sizes they have grown to (inbox_slot_runs, exchange_slot_runs and
+ * exchange_send_runs do not shrink; no output depends on them), and the transport counters
+ * (inbox_grows, exchange_slot_grows, exchange_spills, inbox_overflow_rounds, inbox_moved_runs,
+ * exchange_bytes, persistent_x_launches) are not rewound.
+ * Everything is checked before anything changes: SGN_EINVAL when snaps[i] is null, is not
+ * ctxs[i]'s, or the snapshots are of different rounds; SGN_ESTATE for a snapshot taken before
+ * the last sgn_sim_init. */
+int sgn_shards_snapshot_restore(sgn_ctx* const* ctxs, uint32_t n, sgn_snapshot* const* snaps /* [n] */);
 
 /* Whole-simulation counters (summed over owned hosts). */
 typedef struct sgn_stats {

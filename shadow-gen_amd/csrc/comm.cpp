@@ -443,6 +443,10 @@ int sgn_run_local_group(sgn_ctx* const* ctxs, uint32_t n, uint64_t max_rounds, u
     }
     for (uint32_t i = 0; i < n && (held || !defer); i++)
       if (int rc = resolve_pools(ctxs[i])) return rc;
+    if (ctxs[0]->paused) {  // (sgn_shards_run_until: every shard held this edge with HOLD_PAUSE)
+      done++;
+      break;
+    }
   }
   // (deferred spills: every run is back in its slab before the caller can ask for next-event
   // times — k_next_packet scans the pool and the extensions, not the spill area)
@@ -457,5 +461,105 @@ int sgn_run_local_group(sgn_ctx* const* ctxs, uint32_t n, uint64_t max_rounds, u
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------
+// Run-control for sharded simulations (sgn_shards_*): the shards of one call are a whole local
+// group in rank order, or the one context of a rank that has a communicator (a collective:
+// every rank makes the same call with the same arguments at the same round edge).
+// ------------------------------------------------------------------------------------
+namespace sgn {
+int shard_set(sgn_ctx* const* ctxs, uint32_t n, const char* what, std::vector<sgn_ctx*>* sh, bool* peers) {
+  if (!ctxs || n == 0) return SGN_EINVAL;
+  for (uint32_t i = 0; i < n; i++)
+    if (!ctxs[i]) return SGN_EINVAL;
+  sgn_ctx* c0 = ctxs[0];
+  const std::string w(what);
+  for (uint32_t i = 0; i < n; i++)
+    if (!ctxs[i]->sim_ready) return set_error(ctxs[i], SGN_ESTATE, "no simulation");
+  if (c0->comm_local) {
+    if (c0->group.size() != n || !std::equal(ctxs, ctxs + n, c0->group.begin()))
+      return set_error(c0, SGN_ESTATE, w + ": needs every context of the local shard group, in rank order");
+    *peers = false;
+  } else if (c0->nranks > 1 && c0->comm) {
+    if (n != 1) return set_error(c0, SGN_ESTATE, w + ": a rank with a communicator passes its one context");
+    *peers = true;
+  } else {
+    return set_error(c0, SGN_ESTATE, w + ": not a sharded context (a local shard group or a rank with a "
+                                         "communicator); a single shard uses the plain call");
+  }
+  for (uint32_t i = 0; i < n; i++)
+    if (!ctxs[i]->failed.empty()) return set_error(ctxs[i], SGN_ESTATE, "simulation unusable: " + ctxs[i]->failed);
+  sh->assign(ctxs, ctxs + n);
+  return 0;
+}
+
+// ranks: min and max of v[0..k) over all ranks, through one grouped all-reduce (lo, hi: k each)
+int comm_agree(sgn_ctx* ctx, const uint64_t* v, size_t k, uint64_t* lo, uint64_t* hi) {
+  std::vector<uint64_t> h(2 * k);
+  for (size_t i = 0; i < k; i++) h[i] = h[k + i] = v[i];
+  void* d = nullptr;
+  SGN_HIP(ctx, hipSetDevice(ctx->device));
+  SGN_HIP(ctx, hipMalloc(&d, 2 * k * 8));
+  hipError_t e = hipMemcpy(d, h.data(), 2 * k * 8, hipMemcpyHostToDevice);
+  int rc = e == hipSuccess ? comm_allreduce_minmax(ctx, (uint64_t*)d, k, k) : 0;
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (!rc && e == hipSuccess) e = hipMemcpy(h.data(), d, 2 * k * 8, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_fail(ctx, e, "all-reduce (run-control)");
+  for (size_t i = 0; i < k; i++) {
+    lo[i] = h[i];
+    hi[i] = h[k + i];
+  }
+  return 0;
+}
+}  // namespace sgn
+
+extern "C" int sgn_shards_run_until(sgn_ctx* const* ctxs, uint32_t n, uint64_t t_emulated, uint64_t* rounds_done) {
+  if (rounds_done) *rounds_done = 0;
+  std::vector<sgn_ctx*> sh;
+  bool peers = false;
+  if (int rc = shard_set(ctxs, n, "sgn_shards_run_until", &sh, &peers)) return rc;
+  sgn_ctx* c0 = sh[0];
+  for (sgn_ctx* c : sh) {
+    c->ctrl_fresh = false;
+    if (int rc = rng_release(c)) return rc;
+    if (int rc = ctrl_sync(c)) return rc;
+  }
+  if (peers) {
+    // every rank must pass the same target: a disagreement is an error on every rank, found
+    // before anything is launched (a round kernel would wait for a peer that paused earlier)
+    uint64_t lo = 0, hi = 0;
+    if (int rc = comm_agree(c0, &t_emulated, 1, &lo, &hi)) return rc;
+    if (lo != hi) return set_error(c0, SGN_EINVAL, "sgn_shards_run_until: the ranks passed different targets");
+  }
+  // (sgn_run_until's rule: the window start is the minimum next event time, the same on every shard)
+  if (!c0->h_ctrl->active || t_emulated <= c0->h_ctrl->ws) return 0;
+  const uint64_t r_start = c0->h_ctrl->rounds;
+  // the same target into every shard's control block (all of them, whatever fails on the way)
+  auto set_pause = [&](uint64_t t) {
+    int rc = 0;
+    for (sgn_ctx* c : sh) {
+      hipError_t e = hipSetDevice(c->device);
+      if (e == hipSuccess) e = hipMemcpy((char*)c->S.ctrl + offsetof(Ctrl, pause_at), &t, 8, hipMemcpyHostToDevice);
+      c->h_ctrl->pause_at = t;
+      c->paused = false;
+      if (!rc && e != hipSuccess) rc = hip_fail(c, e, "hipMemcpy(pause_at)");
+    }
+    return rc;
+  };
+  int rc = set_pause(t_emulated);
+  // the group's normal path: rounds still held are resolved first, a persistent launch ends at
+  // the paused edge on every shard, queued per-round launches turn into no-ops
+  if (!rc) rc = peers ? sgn_run(c0, ~0ull, nullptr) : sgn_run_local_group(ctxs, n, ~0ull, nullptr);
+  const int rc_clear = set_pause(EMU_MAX);  // (also after a failure: no later run may pause)
+  if (rc || (rc = rc_clear)) return rc;
+  for (sgn_ctx* c : sh) {
+    c->ctrl_fresh = false;
+    if ((rc = ctrl_sync(c))) return rc;
+  }
+  if (rounds_done) *rounds_done = c0->h_ctrl->rounds - r_start;
+  return 0;
+}
 
 uint64_t sgn::layout_sig_comm() { return kLayoutSig; }

@@ -3908,13 +3908,16 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
   struct RoundLDS {
     uint64_t ws, we, pend_ws, pend_we, pend_nb1, pg_avail;
     uint64_t pg_alloc, occ, hold_need;
-    uint32_t active, ks, pend, pend_new, ngap, hold;
+    uint64_t pause_at;           // Ctrl::pause_at as of the launch (sgn_shards_run_until)
+    uint32_t ks, pend_new, ngap, hold;
+    // (flags, as half words: with them pause_at costs this kernel no LDS — config C's grid stays
+    // resident only while the static LDS stays within its 512-byte granule)
+    uint16_t active, pend, fpend, fbuf;  // fpend, fbuf: imports left for the next round's start
+                                         // (and their slot parity; their horizon: the round pend_ws started)
     // runs to file from the inbox slots this round: in all, and from each shard (nin, from the
     // exchange until they are filed); while the workgroup executes, nin counts its runs to each
     // shard instead (OutboxHdr::xc; reset after the filing, flushed at the arrival)
     uint32_t n_in, nin[XR_MAX];
-    uint32_t fpend, fbuf;        // imports left for the next round's start (and their slot parity;
-                                 // their horizon: the round pend_ws started)
     uint32_t last;               // this workgroup arrived last at the shard's local barrier
   };
   __shared__ RoundLDS rs;
@@ -3922,7 +3925,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
     rs.pg_avail = ld_dev(&C->pg_avail);
     rs.ws = ld_dev(&C->ws);
     rs.we = ld_dev(&C->we);
-    rs.active = ld_dev(&C->active);
+    rs.active = (uint16_t)ld_dev(&C->active);
     rs.ks = ld_dev(&C->keep_slab);
     rs.pend = 0;
     rs.ngap = 0;
@@ -3930,6 +3933,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
     rs.occ = ld_dev(&C->cal_occ);
     rs.hold = ld_dev(&C->hold);
     rs.hold_need = ld_dev(&C->hold_need);
+    rs.pause_at = ld_dev(&C->pause_at);  // (read once; the host writes every shard the same target)
     rs.fpend = 0;
     rs.n_in = 0;
     rs.last = 0;
@@ -4236,6 +4240,8 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
       if (spill_any) hflags |= HOLD_SPILL;
       if (xmax > S.xislot) hflags |= HOLD_XSLOT;
       else if (2 * xmax > S.xislot) hflags |= HOLD_XGROW;
+      // (min_next is the messages' minimum: every workgroup of every shard decides alike)
+      if (min_next >= rs.pause_at) hflags |= HOLD_PAUSE;
     }
     // this shard's own round edge, from its message to itself
     const uint64_t e_nb1 = xw(XH_NB1, me), e_occd = xw(XH_OCCD, me), e_nalloc = xw(XH_NALLOC, me),
@@ -4385,7 +4391,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
       st_dev(&C->keep_slab, rs.ks);
       st_dev(&C->ws, rs.ws);
       st_dev(&C->we, rs.we);
-      st_dev(&C->active, rs.active);
+      st_dev(&C->active, (uint32_t)rs.active);
       st_dev(&C->rounds, rounds0 + r);
       st_dev(&C->pg_avail, rs.pg_avail);
       st_dev(&C->cal_occ, rs.occ);
@@ -4518,6 +4524,8 @@ __global__ __launch_bounds__(256) void k_import(DevSim S) {
     if ((msg[3] >> 32) & 1) hflags |= HOLD_SPILL;
     if (q == S.rank) own = need;
   }
+  // (sgn_shards_run_until: the window every shard just computed from the same messages)
+  if (C->ws >= C->pause_at) hflags |= HOLD_PAUSE;
   if (hflags) {
     C->hold = hflags;
     C->hold_need = own;
@@ -5618,7 +5626,7 @@ int run_xpersist(const std::vector<sgn_ctx*>& sh, bool peers, uint64_t max_round
   int rc = 0;
   // (a round still held from an earlier call: its pools first)
   if (!rc) rc = x_resolve(sh, peers);
-  while (!rc && c0->h_ctrl->active && enq < max_rounds) {
+  while (!rc && c0->h_ctrl->active && enq < max_rounds && !c0->paused) {
     const uint32_t n = (uint32_t)std::min<uint64_t>(kPersistRounds, max_rounds - enq);
     const int lr = x_launch(sh, peers, n);
     if (lr < 0) return lr;
@@ -5642,6 +5650,45 @@ int run_xpersist(const std::vector<sgn_ctx*>& sh, bool peers, uint64_t max_round
     if (c->S.xout_n) (void)hipMemsetAsync((void*)c->S.xout_n, 0, (6 * (size_t)c->nranks + 8) * 4, c->stream);
   if (rounds_done) *rounds_done = c0->h_ctrl->rounds - r_start;
   return rc;
+}
+
+// A resolved round edge on every shard of sh (sgn_shards_*): what the run loops do between their
+// launches. A round k_import held for a full-slot exchange is completed first (RCCL transport; a
+// local group completes it inside sgn_run_local_group and never returns with one), then the held
+// flags: inbox overflow and growth across the shards, each shard's own pools and re-layout.
+int shards_resolve(const std::vector<sgn_ctx*>& sh, bool peers) {
+  for (sgn_ctx* c : sh) {
+    c->ctrl_fresh = false;
+    if (int rc = sync_ctrl(c)) return rc;
+    if (!c->h_ctrl->xspill) continue;
+    if (!peers)
+      return set_error(c, SGN_ESTATE, "a round's full-slot exchange is incomplete: run the group first");
+    if (int rc = comm_complete_spill(c)) return rc;
+  }
+  bool held = false;
+  for (sgn_ctx* c : sh) held = held || c->h_ctrl->hold || c->h_ctrl->spill_n;
+  if (!held) return 0;
+  if (int rc = x_resolve(sh, peers)) return rc;
+  for (sgn_ctx* c : sh)
+    if (int rc = sync_ctrl(c)) return rc;
+  return 0;
+}
+
+// The exchange layer after a shard's state went back to a snapshot (sgn_shards_snapshot_restore).
+// The inbox keeps its size and its mappings, but its message granules carry the global round
+// number as their tag and the rewound rounds repeat those numbers: a receiver would take the
+// first pass's message for the round's. The headers are zeroed (no tag matches a round, as in a
+// new inbox). Slots and bins hold no run at a launch's end; the census words carry launch epochs.
+int xlayer_rewind(sgn_ctx* ctx) {
+  const DevSim& S = ctx->S;
+  if (ctx->xin_mem) {
+    const XLay l = xlay(ctx->nranks, S.xislot, S.G, S.xbk);
+    SGN_HIP(ctx, hipMemsetAsync((char*)ctx->xin_mem + l.hdr, 0, l.cen - l.hdr, ctx->stream));
+  }
+  // (the per-round path counts its sends in row 0 from zero: run_xpersist's end)
+  if (S.xout_n) SGN_HIP(ctx, hipMemsetAsync((void*)S.xout_n, 0, (6 * (size_t)ctx->nranks + 8) * 4, ctx->stream));
+  if (ctx->gexec && ctx->gsz != ctx->xsz_cur) drop_graph(ctx);
+  return 0;
 }
 
 void free_sim(sgn_ctx* ctx) {

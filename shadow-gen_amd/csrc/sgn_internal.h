@@ -149,8 +149,9 @@ struct Ctrl {
   uint32_t res_xverdict;
   uint64_t hold_need;
   uint64_t rnd_alloc, rnd_spill;  // per-round launches: the Outbox counters' target (unread)
-  // sgn_run_until: the single-shard round edges hold (HOLD_PAUSE) once the next window starts
-  // at or after this time; EMU_MAX = never (sgn_run, sgn_round)
+  // sgn_run_until, sgn_shards_run_until: every round edge (single shard, k_rounds_x, k_import)
+  // holds with HOLD_PAUSE once the next window starts at or after this time — the same time on
+  // every shard of a sharded run; EMU_MAX = never (sgn_run, sgn_round, sgn_run_local_group)
   uint64_t pause_at;
 };
 
@@ -164,7 +165,7 @@ enum : uint32_t {
   HOLD_XSLOT = 4u,  // persistent multi-shard: some shard sent a peer more runs than its inbox slot
                     // holds (the rest wait in the sender's spill area: the host moves them)
   HOLD_XGROW = 8u,  // persistent multi-shard: a round used more than half an inbox slot (grow)
-  HOLD_PAUSE = 16u, // single shard: the next window starts at or after Ctrl::pause_at (sgn_run_until)
+  HOLD_PAUSE = 16u, // the next window starts at or after Ctrl::pause_at (sgn_run_until, sgn_shards_run_until)
 };
 
 enum : uint32_t {
@@ -776,7 +777,8 @@ struct sgn_ctx {
   // (sgn_sim_init count) that tags them — a snapshot of an earlier simulation is refused
   std::vector<sgn_snapshot*> snapshots;
   uint64_t sim_gen = 0;
-  bool paused = false;  // the last held round edge carried HOLD_PAUSE (sgn_run_until stops on it)
+  bool paused = false;  // the last held round edge carried HOLD_PAUSE (sgn_run_until and
+                        // sgn_shards_run_until stop on it)
 
   ~sgn_ctx();
 };
@@ -815,6 +817,13 @@ void xinbox_release(sgn_ctx* ctx);
 int xpeer_upload(sgn_ctx* ctx);  // the XPeer table from ctx->x_base (and the RCCL send blocks)
 bool xpersist_possible(sgn_ctx* ctx);
 int run_xpersist(const std::vector<sgn_ctx*>& sh, bool peers, uint64_t max_rounds, uint64_t* rounds_done);
+// the collective run-control calls (sgn_shards_*; comm.cpp, snapshot.hip): the shards of one call
+// (a whole local group in rank order, or a rank's one context: *peers), a resolved round edge on
+// all of them, and the exchange layer after a restore
+int shard_set(sgn_ctx* const* ctxs, uint32_t n, const char* what, std::vector<sgn_ctx*>* sh, bool* peers);
+int shards_resolve(const std::vector<sgn_ctx*>& sh, bool peers);
+int xlayer_rewind(sgn_ctx* ctx);
+int comm_agree(sgn_ctx* ctx, const uint64_t* v, size_t k, uint64_t* lo, uint64_t* hi);  // ranks: min, max of v[i]
 int comm_xpeer_map(sgn_ctx* ctx);       // one shard per GPU: map every peer's inbox (collective)
 int comm_xmove_spills(sgn_ctx* ctx, const std::vector<std::vector<EvRec>>& out,
                       std::vector<EvRec>* in);  // runs past an inbox slot, to their shards (collective)

@@ -295,13 +295,11 @@ void sgn::snapshots_release(sgn_ctx* ctx) {
   ctx->snapshots.clear();
 }
 
-extern "C" {
+namespace {
 
-int sgn_snapshot_save(sgn_ctx* ctx, sgn_snapshot** out) {
-  if (out) *out = nullptr;
-  if (!ctx || !out) return ctx ? set_error(ctx, SGN_EINVAL, "sgn_snapshot_save: null argument") : SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  if (ctx->nranks > 1 || ctx->comm_local) return sharded(ctx, "sgn_snapshot_save");
+// One context's snapshot. A shard of a sharded run comes here from sgn_shards_snapshot_save with
+// its round edge already resolved across the shards.
+int save_one(sgn_ctx* ctx, sgn_snapshot** out) {
   SGN_HIP(ctx, hipSetDevice(ctx->device));
   // CPU-held RNG states back to the device, then a resolved round edge (what sgn_run does on entry)
   if (int e = rng_release(ctx)) return e;
@@ -420,15 +418,22 @@ int sgn_snapshot_save(sgn_ctx* ctx, sgn_snapshot** out) {
   return 0;
 }
 
-int sgn_snapshot_restore(sgn_ctx* ctx, const sgn_snapshot* snap) {
-  if (!ctx || !snap) return ctx ? set_error(ctx, SGN_EINVAL, "sgn_snapshot_restore: null argument") : SGN_EINVAL;
+// what a restore checks before it touches anything (what: the entry point's name)
+int restore_check(sgn_ctx* ctx, const sgn_snapshot* snap, const char* what, sgn_snapshot** s_out) {
+  const std::string w(what);
   sgn_snapshot* s = owned(ctx, snap);
-  if (!s) return set_error(ctx, SGN_EINVAL, "sgn_snapshot_restore: not a snapshot of this context");
+  if (!s) return set_error(ctx, SGN_EINVAL, w + ": not a snapshot of this context");
   if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  if (ctx->nranks > 1 || ctx->comm_local) return sharded(ctx, "sgn_snapshot_restore");
   if (s->gen != ctx->sim_gen)
-    return set_error(ctx, SGN_ESTATE, "sgn_snapshot_restore: the snapshot was taken before the last sgn_sim_init");
+    return set_error(ctx, SGN_ESTATE, w + ": the snapshot was taken before the last sgn_sim_init");
   if (!ctx->failed.empty()) return set_error(ctx, SGN_ESTATE, "simulation unusable: " + ctx->failed);
+  *s_out = s;
+  return 0;
+}
+
+// One context back to its snapshot s (checked by restore_check). shard: a shard of a sharded run
+// — the exchange words of the control block belong to the launch sequence and stay live.
+int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
   SGN_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   SGN_HIP(ctx, hipStreamSynchronize(st));
@@ -550,6 +555,15 @@ int sgn_snapshot_restore(sgn_ctx* ctx, const sgn_snapshot* snap) {
   c.res_verdict = live.res_verdict;
   c.res_xverdict = live.res_xverdict;
   c.epoch = live.epoch;
+  if (shard) {
+    // the exchange layer is not rewound (inboxes, slots and send size keep their live sizes):
+    // the send size the per-round path moves, the largest per-peer count the sizes follow, and
+    // no round waiting for a full-slot exchange (a restore starts from a resolved edge)
+    c.xsz = live.xsz;
+    c.xhwm = live.xhwm;
+    c.xspill = 0;
+    c.imp_done = 0;
+  }
   c.hold = 0;
   c.pause_at = EMU_MAX;
   *ctx->h_ctrl = c;
@@ -573,6 +587,123 @@ int sgn_snapshot_restore(sgn_ctx* ctx, const sgn_snapshot* snap) {
   ctx->codel_allocs_before = s->codel_allocs_before;
   ctx->paused = false;
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sgn_snapshot_save(sgn_ctx* ctx, sgn_snapshot** out) {
+  if (out) *out = nullptr;
+  if (!ctx || !out) return ctx ? set_error(ctx, SGN_EINVAL, "sgn_snapshot_save: null argument") : SGN_EINVAL;
+  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
+  if (ctx->nranks > 1 || ctx->comm_local) return sharded(ctx, "sgn_snapshot_save");
+  return save_one(ctx, out);
+}
+
+int sgn_snapshot_restore(sgn_ctx* ctx, const sgn_snapshot* snap) {
+  if (!ctx || !snap) return ctx ? set_error(ctx, SGN_EINVAL, "sgn_snapshot_restore: null argument") : SGN_EINVAL;
+  sgn_snapshot* s = owned(ctx, snap);
+  if (!s) return set_error(ctx, SGN_EINVAL, "sgn_snapshot_restore: not a snapshot of this context");
+  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
+  if (ctx->nranks > 1 || ctx->comm_local) return sharded(ctx, "sgn_snapshot_restore");
+  if (int rc = restore_check(ctx, snap, "sgn_snapshot_restore", &s)) return rc;
+  return restore_one(ctx, s, false);
+}
+
+// ---- sharded runs: the same two operations over every shard at one round edge ----------------
+int sgn_shards_snapshot_save(sgn_ctx* const* ctxs, uint32_t n, sgn_snapshot** out) {
+  if (out && ctxs)
+    for (uint32_t i = 0; i < n; i++) out[i] = nullptr;
+  if (!out) return SGN_EINVAL;
+  std::vector<sgn_ctx*> sh;
+  bool peers = false;
+  if (int rc = shard_set(ctxs, n, "sgn_shards_snapshot_save", &sh, &peers)) return rc;
+  sgn_ctx* c0 = sh[0];
+  for (sgn_ctx* c : sh) {
+    SGN_HIP(c, hipSetDevice(c->device));
+    if (int rc = rng_release(c)) return rc;
+  }
+  // a resolved round edge everywhere: no run waits in a sender's spill area for a peer's inbox,
+  // no bin or slot holds one (a launch's end), every shard's calendar is within its slabs
+  if (int rc = shards_resolve(sh, peers)) return rc;
+  for (sgn_ctx* c : sh) c->paused = false;
+  // every shard at the same round and window (ranks: by an all-reduce of min and max)
+  {
+    const Ctrl& a = *c0->h_ctrl;
+    uint64_t v[3] = {a.rounds, a.ws, a.we}, lo[3] = {v[0], v[1], v[2]}, hi[3] = {v[0], v[1], v[2]};
+    for (sgn_ctx* c : sh) {
+      const uint64_t w[3] = {c->h_ctrl->rounds, c->h_ctrl->ws, c->h_ctrl->we};
+      for (int k = 0; k < 3; k++) {
+        lo[k] = std::min(lo[k], w[k]);
+        hi[k] = std::max(hi[k], w[k]);
+      }
+    }
+    if (peers)
+      if (int rc = comm_agree(c0, v, 3, lo, hi)) return rc;
+    if (lo[0] != hi[0] || lo[1] != hi[1] || lo[2] != hi[2])
+      return set_error(c0, SGN_ESTATE, "sgn_shards_snapshot_save: the shards do not stand at the same round edge");
+  }
+  int rc = 0;
+  for (uint32_t i = 0; i < n && !rc; i++) rc = save_one(sh[i], &out[i]);
+  if (peers) {  // all or nothing across the ranks too
+    uint64_t bad = rc ? 1 : 0;
+    const int rc2 = comm_allreduce_max_u64(c0, &bad, 1);
+    if (!rc && rc2) rc = rc2;
+    if (!rc && bad) rc = set_error(c0, SGN_ESTATE, "sgn_shards_snapshot_save: another rank's snapshot failed");
+  }
+  if (rc)
+    for (uint32_t i = 0; i < n; i++) {
+      if (out[i]) sgn_snapshot_free(sh[i], out[i]);
+      out[i] = nullptr;
+    }
+  return rc;
+}
+
+int sgn_shards_snapshot_restore(sgn_ctx* const* ctxs, uint32_t n, sgn_snapshot* const* snaps) {
+  if (!snaps) return SGN_EINVAL;
+  std::vector<sgn_ctx*> sh;
+  bool peers = false;
+  if (int rc = shard_set(ctxs, n, "sgn_shards_snapshot_restore", &sh, &peers)) return rc;
+  sgn_ctx* c0 = sh[0];
+  // everything is validated before anything changes
+  std::vector<sgn_snapshot*> ss(n, nullptr);
+  int rc = 0;
+  for (uint32_t i = 0; i < n && !rc; i++) {
+    if (!snaps[i]) rc = set_error(sh[i], SGN_EINVAL, "sgn_shards_snapshot_restore: null snapshot");
+    else rc = restore_check(sh[i], snaps[i], "sgn_shards_snapshot_restore", &ss[i]);
+  }
+  for (uint32_t i = 1; i < n && !rc; i++)
+    if (ss[i]->info.rounds != ss[0]->info.rounds || ss[i]->info.window_start != ss[0]->info.window_start)
+      rc = set_error(sh[i], SGN_EINVAL, "sgn_shards_snapshot_restore: the snapshots are of different round edges");
+  if (peers) {
+    // (stream-ordered after this rank's last launch: when it returns, no peer's kernel still
+    // writes this rank's inbox) every rank valid, and every rank's snapshot of the same round
+    uint64_t v[2] = {rc ? 1ull : 0ull, rc ? 0ull : ss[0]->info.rounds}, lo[2], hi[2];
+    if (int rc2 = comm_agree(c0, v, 2, lo, hi)) return rc ? rc : rc2;
+    if (!rc && hi[0]) rc = set_error(c0, SGN_ESTATE, "sgn_shards_snapshot_restore: refused on another rank");
+    if (!rc && lo[1] != hi[1])
+      rc = set_error(c0, SGN_EINVAL, "sgn_shards_snapshot_restore: the ranks' snapshots are of different round edges");
+  }
+  if (rc) return rc;
+  for (uint32_t i = 0; i < n && !rc; i++) {
+    rc = restore_one(sh[i], ss[i], true);
+    if (!rc) rc = xlayer_rewind(sh[i]);
+    if (!rc && hipStreamSynchronize(sh[i]->stream) != hipSuccess) rc = set_error(sh[i], SGN_EDEVICE, "restore: exchange layer");
+  }
+  if (rc)  // (a shard went back and another did not: no round can run on this group)
+    for (sgn_ctx* c : sh)
+      if (c->failed.empty()) c->failed = "sgn_shards_snapshot_restore failed half way";
+  if (peers) {  // no rank launches a round into an inbox its owner has not yet reset
+    uint64_t bad = rc ? 1 : 0;
+    const int rc2 = comm_allreduce_max_u64(c0, &bad, 1);
+    if (!rc && rc2) rc = rc2;
+    if (!rc && bad) {
+      c0->failed = "sgn_shards_snapshot_restore failed on another rank";
+      rc = set_error(c0, SGN_ESTATE, c0->failed);
+    }
+  }
+  return rc;
 }
 
 void sgn_snapshot_free(sgn_ctx* ctx, sgn_snapshot* snap) {

@@ -296,6 +296,9 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         "sgn_snapshot_restore": (C.c_int, [vp, vp]),
         "sgn_snapshot_free": (None, [vp, vp]),
         "sgn_snapshot_info_get": (C.c_int, [vp, C.POINTER(SnapshotInfo)]),
+        "sgn_shards_run_until": (C.c_int, [C.POINTER(vp), C.c_uint32, C.c_uint64, u64p]),
+        "sgn_shards_snapshot_save": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
+        "sgn_shards_snapshot_restore": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -589,6 +592,49 @@ class Context:
         k = KernelTimes()
         self.check(self.L.sgn_kernel_times_get(self.h, C.byref(k)))
         return {k.name[i].decode(): int(k.launches_total[i]) for i in range(k.n_kernels)}
+
+
+# ------------------------------------------------------------------------------------
+# Run-control for sharded simulations. shards: this process's shards, as sgn_shards_* take them —
+# every Context of a local group in rank order, or [the one Context of a rank with a communicator]
+# (then a collective: every rank makes the same call).
+# ------------------------------------------------------------------------------------
+
+def _shard_array(shards):
+    return (C.c_void_p * len(shards))(*[c.h.value for c in shards])
+
+
+def _shards_call(shards, name, *args):
+    """fn(ctxs, n, *args); the library reports an error on the context it refused: the one whose
+    last error changed speaks."""
+    errs = lambda: [c.L.sgn_last_error(c.h).decode() for c in shards]  # noqa: E731
+    before = errs()
+    rc = getattr(shards[0].L, name)(_shard_array(shards), len(shards), *args)
+    if rc != 0:
+        after = errs()
+        new = [a for a, b in zip(after, before) if a != b] or [a for a in after if a]
+        raise SgnError(rc, new[0] if new else name + ": invalid argument")
+
+
+def shards_run_until(shards, t_emulated):
+    """Runs every shard until the next window would start at or after t_emulated (or the end);
+    returns the rounds run (the same on every shard)."""
+    d = C.c_uint64()
+    _shards_call(shards, "sgn_shards_run_until", t_emulated, C.byref(d))
+    return d.value
+
+
+def shards_snapshot_save(shards):
+    """One snapshot handle per shard, all of the same round edge (snaps[i] is owned by shards[i]:
+    Context.snapshot_info / snapshot_free apply)."""
+    out = (C.c_void_p * len(shards))()
+    _shards_call(shards, "sgn_shards_snapshot_save", out)
+    return [C.c_void_p(v) for v in out]
+
+
+def shards_snapshot_restore(shards, snaps):
+    arr = (C.c_void_p * len(snaps))(*[s.value if isinstance(s, C.c_void_p) else s for s in snaps])
+    _shards_call(shards, "sgn_shards_snapshot_restore", arr)
 
 
 # ------------------------------------------------------------------------------------

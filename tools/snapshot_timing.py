@@ -5,9 +5,13 @@ calendar, the time a raw device-to-device copy of the unpacked calendar takes in
 (what a snapshot without packing would pay for the calendar alone), and the only way back there
 was before snapshots: sgn_sim_init + sgn_run to the same round.
 
-usage: python tools/snapshot_timing.py [--workload C D] [--rounds 1500] [--out FILE]
-The save is taken after bench.py's warm-up + steps worth of rounds (5 + 10 steps of 100)."""
+usage: python tools/snapshot_timing.py [--workload C D] [--rounds 1500] [--shards N] [--out FILE]
+The save is taken after bench.py's warm-up + steps worth of rounds (5 + 10 steps of 100).
+--shards N: the same hosts as N shards of one local group on this GPU, saved and restored with
+the collective calls (sgn_shards_snapshot_*): per-shard save times (their maximum and their sum:
+the shards save one after the other) and the wall time of the group's save and restore."""
 import argparse
+import ctypes as C
 import json
 import pathlib
 import sys
@@ -92,13 +96,67 @@ def measure(name, rounds):
     }
 
 
+def measure_group(name, rounds, k):
+    g, used, hosts, cfg, tr = workload(name, rounds)
+    cfg = type(cfg).from_buffer_copy(cfg)
+    cfg.event_capacity = -(-cfg.event_capacity // k)  # (the calendar is sized per shard)
+    shards = [sgn.Context(device=0, shard_rank=r, shard_count=k) for r in range(k)]
+    arr = (C.c_void_p * k)(*[c.h.value for c in shards])
+    for c in shards:
+        c.routes_build(g, used)
+        c.hosts_set(hosts)
+    shards[0].check(shards[0].L.sgn_comm_init_local(arr, k, 1 << 13))
+    for c in shards:
+        c.sim_init(cfg, tr)
+
+    def run(nr):
+        d = C.c_uint64()
+        shards[0].check(shards[0].L.sgn_run_local_group(arr, k, nr, C.byref(d)))
+        return d.value
+
+    done = run(rounds)
+    w = shards[0].window()
+    for c, s in zip(shards, sgn.shards_snapshot_save(shards)):
+        c.snapshot_free(s)
+    t0 = time.perf_counter()
+    snaps = sgn.shards_snapshot_save(shards)  # (the second save: allocations and code objects warm)
+    save_wall_ms = (time.perf_counter() - t0) * 1e3
+    infos = [c.snapshot_info(s) for c, s in zip(shards, snaps)]
+    run(200)
+    t0 = time.perf_counter()
+    sgn.shards_snapshot_restore(shards, snaps)
+    restore_ms = (time.perf_counter() - t0) * 1e3
+    assert all(c.window() == w and c.stats()["rounds"] == done for c in shards)
+    eng = [c.engine_info() for c in shards]
+    for c, s in zip(shards, snaps):
+        c.snapshot_free(s)
+    for c in shards:
+        c.close()
+    return {
+        "tool": "snapshot_timing", "build_id": sgn.build_id(), "workload": name, "hosts": hosts.n, "shards": k,
+        "rounds_at_save": done, "save_ms_max": round(max(i["save_ms"] for i in infos), 3),
+        "save_ms_sum": round(sum(i["save_ms"] for i in infos), 3),
+        "pack_ms_sum": round(sum(i["pack_ms"] for i in infos), 3), "save_wall_ms": round(save_wall_ms, 3),
+        "restore_wall_ms": round(restore_ms, 3), "device_bytes": sum(i["device_bytes"] for i in infos),
+        "calendar_runs": sum(i["calendar_runs"] for i in infos),
+        "calendar_bytes": sum(i["calendar_bytes"] for i in infos),
+        "calendar_pool_bytes": sum(i["calendar_pool_bytes"] for i in infos),
+        "exchange_mode": eng[0]["exchange_mode"], "inbox_slot_runs": eng[0]["inbox_slot_runs"],
+        "sim_device_bytes": sum(e["device_bytes"] for e in eng),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", nargs="+", choices=("C", "D"), default=["C", "D"])
     ap.add_argument("--rounds", type=int, default=1500)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--shards", type=int, default=1)
     args = ap.parse_args()
-    lines = [json.dumps(measure(w, args.rounds)) for w in args.workload]
+    if args.shards > 1:
+        lines = [json.dumps(measure_group(w, args.rounds, args.shards)) for w in args.workload]
+    else:
+        lines = [json.dumps(measure(w, args.rounds)) for w in args.workload]
     for ln in lines:
         print(ln, flush=True)
     if args.out:
