@@ -255,7 +255,11 @@ int sgn_run(sgn_ctx* ctx, uint64_t max_rounds, uint64_t* rounds_done);
  * when min_next_event_time >= target" (manager.rs:1372-1382). t_emulated at or below the current
  * window start runs nothing (rounds_done = 0). The comparison runs on the device at every round
  * edge, so persistent launches still run many rounds each; sgn_run and sgn_round never pause.
- * rounds_done may be NULL. */
+ * rounds_done may be NULL.
+ * With SGN_TRAFFIC_EXTERNAL traffic the call runs the datagrams already submitted: before
+ * running to t_emulated, submit every datagram with send_time < t_emulated + the longest window
+ * (see sgn_submit, "Submitting ahead"); the call returns early, inactive, when the device has
+ * no event left, and sgn_set_window + sgn_submit continue from there. */
 int sgn_run_until(sgn_ctx* ctx, uint64_t t_emulated, uint64_t* rounds_done);
 
 /* A snapshot of the simulation. Opaque; owned by the context it came from (sgn_snapshot_free, or
@@ -430,7 +434,26 @@ int sgn_trace_read(sgn_ctx* ctx, sgn_trace_rec* out, uint64_t cap, uint64_t* n_t
  * packet.rs:617-635; the wire length feeds the token buckets and CoDel's byte count, and a
  * zero-payload segment is never loss-dropped, worker.rs:371). handle is opaque
  * (the payload stays on the CPU) and comes back in the packet's drain record. Call between
- * rounds; a failed call queues nothing. Replaces Worker::send_packet's CPU callers. */
+ * rounds; a failed call queues nothing. Replaces Worker::send_packet's CPU callers.
+ *
+ * Submitting ahead. A controller need not submit window by window: any send_time below the
+ * horizon — window start + (calendar_buckets - 2) * bucket_width_ns, both from
+ * sgn_engine_info_get — is accepted, and sgn_run / sgn_run_until / sgn_run_local_group /
+ * sgn_shards_run_until then run many rounds per call (the persistent round kernels) with the
+ * datagrams taken at their times; windows and fates are those of submitting each window's
+ * datagrams just before its round. What must be in before running to a time T: every datagram
+ * with send_time < T + the longest window (runahead_ns; with use_dynamic_runahead, the longest
+ * route latency if that is more), because the last window of such a run starts below T and may
+ * end that much past it — a datagram submitted later would find its window gone (send_time
+ * below the window start: SGN_EINVAL). When the simulation has run dry, or the next send lies
+ * before the device's next event, sgn_set_window moves the window to it as before.
+ * Shards: a datagram goes to the shard that owns src_host (anything else is SGN_EINVAL). Each
+ * shard numbers its own submissions, so the slot bits of a drain record's tag (tag &
+ * SGN_TAG_SLOT_MASK) are per submitting shard, and the record carries the submitted handle
+ * only where the shard that drains it also submitted it: fates decided at the source (LOCAL,
+ * LOSS, UNKNOWN, BLOCKED) always do; DELIVERED and CODEL records, which appear at the
+ * destination, carry handle 0 when the destination belongs to another shard (src_host and
+ * src_eid identify the datagram there). */
 typedef struct sgn_pkt_soa {
   uint64_t n;
   const uint32_t* src_host;    /* [n] HostId */

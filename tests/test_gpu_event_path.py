@@ -8,7 +8,7 @@ the places that use them run at their extremes:
     datagram at a time (PERIODIC);
   * the CoDel free ring's counters pass several multiples of the pool size (the ring index is
     counter mod cq_pages by cq_pages' reciprocal) and the pool grows (the reciprocal changes);
-  * the same with the diagnostic stamps on.
+  * the same with the diagnostic stamps on, and CPU-submitted datagrams (EXTERNAL) with them on.
 """
 import numpy as np
 import pytest
@@ -75,10 +75,19 @@ def test_codel_ring_wraps_and_pool_grows(ctxf, oracle, monkeypatch, persistent):
     assert_same_run(o, c, N, trace=False)
 
 
-@pytest.mark.parametrize("kind", ["default", "tgen"])
+@pytest.mark.parametrize("kind", ["default", "tgen", "external"])
 def test_stamps_on_is_bit_exact(ctxf, oracle, monkeypatch, kind):
     # the diagnostic stamps are read by the host only: a run with them on computes the same
     monkeypatch.setenv("SGN_STAMPS", "1")
+    if kind == "external":
+        # CPU-submitted datagrams, submitted ahead and run many rounds per call (k_rounds_diag<EXTERNAL>):
+        # test_gpu_external's CoDel world, every drain record compared on the way
+        from test_gpu_external import run_case
+        o, c, _, _ = run_case(ctxf, oracle, "codel", flags=sgn.CREATE_TIME_KERNELS)
+        assert c.stats()["packets_sent"] > 1000
+        assert c.kernel_times()["k_rounds"][0] > 0, c.kernel_times()
+        assert_same_run(o, c, 60, trace=False)
+        return
     if kind == "default":
         args, n = scenario(), 200
     else:
