@@ -134,7 +134,9 @@ int sgn_create(sgn_ctx** out, const sgn_create_opts* opts) {
     return SGN_EINVAL;
   }
   if (sgn::layout_sig_engine() != kLayoutSig || sgn::layout_sig_routes() != kLayoutSig ||
-      sgn::layout_sig_comm() != kLayoutSig) {
+      sgn::layout_sig_comm() != kLayoutSig || sgn::layout_sig_sim_init() != kLayoutSig ||
+      sgn::layout_sig_run() != kLayoutSig || sgn::layout_sig_pools() != kLayoutSig ||
+      sgn::layout_sig_interop() != kLayoutSig) {
     g_create_error = "libsgn's objects were compiled against different versions of sgn_internal.h (rebuild all of them)";
     return SGN_ESTATE;
   }

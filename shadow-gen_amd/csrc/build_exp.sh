@@ -10,4 +10,5 @@ HIPCC=/opt/rocm/bin/hipcc
 make -s -j8 ../libsgn.so
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -Wno-unused-value -I../../include -I."
 $HIPCC $F $2 -c engine.hip -o engine_exp_$1.o
-$HIPCC --offload-arch=gfx950 -shared -o ../libsgn_exp_$1.so api.o routes.o engine_exp_$1.o snapshot.o frontend.o comm.o pcap.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+# (the Makefile's host objects: only engine.hip is compiled with the variant's flags)
+$HIPCC --offload-arch=gfx950 -shared -o ../libsgn_exp_$1.so engine_exp_$1.o $(make -s print-host-objs) -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib

@@ -23,11 +23,6 @@
 
 #include "sgn_internal.h"
 
-namespace sgn {
-void launch_execute(sgn_ctx* ctx);
-void launch_import(sgn_ctx* ctx);
-}  // namespace sgn
-
 using namespace sgn;
 
 static_assert(sizeof(ncclUniqueId) <= SGN_COMM_ID_BYTES, "ncclUniqueId size");
@@ -73,10 +68,6 @@ int sgn_comm_init(sgn_ctx* ctx, const uint8_t id[SGN_COMM_ID_BYTES], uint64_t sl
 }  // extern "C"
 
 namespace sgn {
-int ctrl_sync(sgn_ctx* ctx);  // engine.hip: the control block to the host, overflow check
-int resolve_pools(sgn_ctx* ctx);  // engine.hip: a held round edge's pool growth
-int grow_exchange_slot(sgn_ctx* ctx);  // engine.hip: larger exchange slots (runs past a slot)
-
 uint64_t comm_round_bytes(const sgn_ctx* ctx) {
   return ctx->nranks > 1 && ctx->comm ? (uint64_t)(ctx->nranks - 1) * ((uint64_t)(XHDR + ctx->xsz_cur) * sizeof(EvRec)) : 0;
 }
@@ -138,7 +129,7 @@ int comm_complete_spill(sgn_ctx* ctx) {
   ctx->xsz_cur = (uint32_t)std::min<uint64_t>(sz, S.xslot);
   SGN_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)&S.ctrl->xsz, (int)ctx->xsz_cur, 1, st));
   ctx->x_spills++;
-  return ctrl_sync(ctx);
+  return sync_ctrl(ctx);
 }
 
 // Sharded APSP (routes.hip): every shard owns a contiguous block of rows (row tiles of the
@@ -421,11 +412,11 @@ int sgn_run_local_group(sgn_ctx* const* ctxs, uint32_t n, uint64_t max_rounds, u
     if (int rc = exchange_import()) return rc;
     // a round some shard spilled runs past a slot in was held by every shard alike: the slots
     // grow (the same size everywhere) and the round is exchanged and imported again
-    if (int rc = ctrl_sync(ctxs[0])) return rc;
+    if (int rc = sync_ctrl(ctxs[0])) return rc;
     if (ctxs[0]->h_ctrl->xspill) {
       for (uint32_t i = 0; i < n; i++) {
         sgn_ctx* c = ctxs[i];
-        if (int rc = ctrl_sync(c)) return rc;
+        if (int rc = sync_ctrl(c)) return rc;
         if (c->h_ctrl->xhwm > c->S.xslot)
           if (int rc = grow_exchange_slot(c)) return rc;
         SGN_HIP(c, hipMemsetD32Async((hipDeviceptr_t)&c->S.ctrl->xspill, 0, 1, c->stream));
@@ -438,11 +429,11 @@ int sgn_run_local_group(sgn_ctx* const* ctxs, uint32_t n, uint64_t max_rounds, u
     // a held round edge (the same on every shard) or a spill: the pools grow before the next
     bool held = false;
     for (uint32_t i = 0; i < n; i++) {
-      if (int rc = ctrl_sync(ctxs[i])) return rc;
+      if (int rc = sync_ctrl(ctxs[i])) return rc;
       held = held || ctxs[i]->h_ctrl->hold;
     }
     for (uint32_t i = 0; i < n && (held || !defer); i++)
-      if (int rc = resolve_pools(ctxs[i])) return rc;
+      if (int rc = resolve_hold(ctxs[i])) return rc;
     if (ctxs[0]->paused) {  // (sgn_shards_run_until: every shard held this edge with HOLD_PAUSE)
       done++;
       break;
@@ -452,9 +443,9 @@ int sgn_run_local_group(sgn_ctx* const* ctxs, uint32_t n, uint64_t max_rounds, u
   // times — k_next_packet scans the pool and the extensions, not the spill area)
   if (defer)
     for (uint32_t i = 0; i < n; i++) {
-      if (int rc = ctrl_sync(ctxs[i])) return rc;
+      if (int rc = sync_ctrl(ctxs[i])) return rc;
       if (ctxs[i]->h_ctrl->spill_n || ctxs[i]->h_ctrl->hold)
-        if (int rc = resolve_pools(ctxs[i])) return rc;
+        if (int rc = resolve_hold(ctxs[i])) return rc;
     }
   if (rounds_done) *rounds_done = pre + done;
   return 0;
@@ -524,7 +515,7 @@ extern "C" int sgn_shards_run_until(sgn_ctx* const* ctxs, uint32_t n, uint64_t t
   for (sgn_ctx* c : sh) {
     c->ctrl_fresh = false;
     if (int rc = rng_release(c)) return rc;
-    if (int rc = ctrl_sync(c)) return rc;
+    if (int rc = sync_ctrl(c)) return rc;
   }
   if (peers) {
     // every rank must pass the same target: a disagreement is an error on every rank, found
@@ -556,7 +547,7 @@ extern "C" int sgn_shards_run_until(sgn_ctx* const* ctxs, uint32_t n, uint64_t t
   if (rc || (rc = rc_clear)) return rc;
   for (sgn_ctx* c : sh) {
     c->ctrl_fresh = false;
-    if ((rc = ctrl_sync(c))) return rc;
+    if ((rc = sync_ctrl(c))) return rc;
   }
   if (rounds_done) *rounds_done = c0->h_ctrl->rounds - r_start;
   return 0;

@@ -443,14 +443,6 @@ struct Pkt {
 // ------------------------------------------------------------------------------------
 // A lane's LDS slot: the pending digest runs and the digests themselves (touched once per
 // run), and the CoDel queue's cached head and open tail runs.
-constexpr uint32_t GATHER_SPEC = 16;  // slab slots a gather loads before the fill is known
-// The round kernels' dynamic LDS before the optional bucket-minimum table: CAP event runs and
-// two u16 index arrays (padded to 8 bytes), at least 1 KB — a big slab's radix select keeps its
-// 256-bin histogram there (exec_group), and test hooks may set CAP below 32
-__host__ __device__ __forceinline__ size_t exec_lds_runs_bytes(uint32_t cap) {
-  const size_t b = (size_t)cap * sizeof(EvRec) + 2 * (size_t)((cap + 3) & ~3u) * 2;
-  return b > 1024 ? b : 1024;
-}
 
 // The wave's outbox: event records for this shard's calendar, placed after the event loop
 // by all 64 lanes at once (one round trip for all the slab reservations of the wave instead
@@ -2192,16 +2184,6 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
   return (uint32_t)__popcll(lane ? (m & ((~0ULL) >> (64 - lane))) : 0ULL);
 }
 
-// The CoDel pages a round over [ws, we) may take. A page is taken only when a CoDel push
-// opens a new run on a full tail page (codel_push_run), and every push is one due event run:
-// a host receiving k runs takes at most ceil(k / 16) pages, so the round takes at most
-// (D + 15 min(D, hosts)) / 16 for D due runs — at most the calendar's runs (occupancy) and at
-// most the slabs of the buckets the window overlaps. A round edge whose free pages fall below
-// this holds before the round (Ctrl::hold) and the host grows the pool: a CoDel queue never
-// refuses a packet (codel_queue.rs:33,303-317 has no limit).
-__host__ __device__ __forceinline__ uint64_t codel_pages_bound(uint64_t due, uint64_t hosts) {
-  return (due + 15 * (due < hosts ? due : hosts) + 15) / 16;
-}
 template <class SV>
 __device__ __forceinline__ uint64_t codel_round_bound(const SV& S, uint64_t occ, uint64_t ws, uint64_t we) {
   const uint32_t nbk = ((bucket_of(S, we - 1) - bucket_of(S, ws)) & (SK(NB) - 1)) + 1;
@@ -3198,7 +3180,6 @@ __global__ __launch_bounds__(64, 2) void k_execute(const DevSim* __restrict__ Sg
 // minimum, the global bucket -> slab table) and before the launch ends; buffer (r + 1) % 3 is
 // reset by workgroup 0 during round r (its last readers passed barrier r - 1). sim_init sizes
 // the calendar so no send of round r + 1 can reach a bucket consumed in round r.
-constexpr uint32_t RB_CH = 64;  // chunk slots per buffer (persistent grids up to 4096 workgroups)
 // Strides between chunks (u32 counters, u64 minimum pairs, u64 occupancy sums). TGEN rounds
 // (config C: 1563 workgroups in 25 chunks) give every chunk its own 128-B line for each, so
 // the ~4.7 k arrival atomics of a round do not queue on a few shared lines: same-box A/B on
@@ -3210,7 +3191,6 @@ template <uint32_t kApp> struct RbLayout {
   static constexpr uint32_t CS = pad ? 32 : 1, MS = pad ? 16 : 2, OS = pad ? 16 : 1;
   static constexpr uint32_t CB = (RB_CH + 1) * CS;  // u32 per buffer of counters (chunks, then the top)
 };
-constexpr uint32_t RB_CS_MAX = 32, RB_MS_MAX = 16, RB_OS_MAX = 16, RB_CB_MAX = (RB_CH + 1) * RB_CS_MAX;
 
 template <uint32_t kApp, class SV>
 __device__ __forceinline__ void rb_arrive(const SV& S, uint32_t p, uint32_t w, uint32_t nw, uint64_t kmin,
@@ -3366,8 +3346,6 @@ __device__ __forceinline__ void rb_reset0(const SV& S, uint32_t nch) {
 // A workgroup of k_rounds that gives up on a barrier (OVF_TIMEOUT) may do so after the
 // bookkeeping workgroup copied the control block into host memory: it also marks the copy
 // stale (the word after the epoch), and the host then reads the device's block.
-static_assert(sizeof(Ctrl) % 8 == 0, "the control block is copied as 8-byte words");
-constexpr uint32_t kMirrorWords = sizeof(Ctrl) / 8 + 2;  // the block, the epoch, the stale mark
 __device__ __forceinline__ void fail_timeout(const DevSim& S) {
   atomicOr((unsigned int*)&SK(ctrl)->overflow, OVF_TIMEOUT);
   if (SK(ctrl_mirror)) st_sys(&SK(ctrl_mirror)[kMirrorWords - 1], 1ull);
@@ -3709,7 +3687,6 @@ __global__ __launch_bounds__(64, 2) void k_rounds_diag(const DevSim* __restrict_
 // may still be filing round r's. Rounds that would need more than a slot, or a larger pool, or a
 // re-layout, are held on every shard alike (the same messages, the same decisions) and the host
 // completes them between launches.
-constexpr uint32_t XR_MAX = 8;  // shards of a persistent multi-shard run (one MI355X node)
 // The round-edge messages across GPUs: a system-scope release before them (kept: it costs
 // nothing measurable), and no system-scope acquire after them. The acquire (buffer_inv sc0 sc1
 // in every workgroup, every round) cost 9 us per round on the two-process rehearsal (41.6 ->
@@ -3730,13 +3707,6 @@ constexpr bool kKxBig = false;
 #else
 constexpr bool kKxBig = true;
 #endif
-// imports of a round up to this many runs are filed by their own workgroups at the next round's
-// start (each workgroup scans them all: ~64 KB), more are shared out before a second barrier
-// (DevSim::xown; SGN_XOWN: a test hook, 0 = always shared)
-constexpr uint32_t kOwnFile = 2048;
-// inbox bins: runs per (round parity, sender, receiving host group). Config C at 8 shards sends
-// a group ~0.6 runs per sender and round, config D ~8; a fuller bin sends the rest to the slot.
-constexpr uint32_t kXBin = 32;
 // shards of up to this many workgroups arrive on one counter (k_rounds' chunk counters take
 // two returning atomics for the last arrival; at config C's ~200 workgroups per shard, spread
 // over the round's ~15 us of arrivals, one counter does not queue)
@@ -4439,9 +4409,6 @@ __device__ __forceinline__ void advance_window(const DevSim& S, Ctrl* C) {
   C->rounds++;
 }
 
-// few blocks: the round's received runs are a few thousand, and every block counts itself in
-// with a device atomic on one word
-constexpr uint32_t kImportBlocks = 16;
 __global__ __launch_bounds__(256) void k_import(DevSim S) {
   Ctrl* C = S.ctrl;
   // every block reads the same values: nothing changes them before all blocks count in
@@ -4692,2436 +4659,83 @@ __global__ void k_next_packet(const DevSim* Sp, uint32_t lo, uint32_t n, uint32_
 }  // namespace sgn
 
 // ====================================================================================
-// Host side: sim init, round launch, readback
+// Launch surface: the only host code of this translation unit (declared in sgn_internal.h).
+// The host half lives in sim_init.cpp, run.cpp, pools.cpp and interop.cpp; it reaches the
+// kernels through the table and the launch functions below and nothing else.
 // ====================================================================================
-using namespace sgn;
-
-namespace {
-
-inline uint64_t host_splitmix(uint64_t& s) {
-  s += 0x9e3779b97f4a7c15ULL;
-  uint64_t z = s;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-  return z ^ (z >> 31);
-}
-
-template <typename T>
-T* dalloc(sgn_ctx* ctx, size_t n) {
-  return (T*)dev_alloc(ctx, n * sizeof(T));
-}
-
-enum { K_EXECUTE = 0, K_IMPORT, K_NUM };
-const char* kKernelNames[K_NUM] = {"k_execute", "k_import"};
-
-int launch_round(sgn_ctx* ctx);
-
-// dynamic LDS of k_execute / k_rounds: CAP event runs + two u16 index arrays
-// (the u16 index arrays are padded to 8 bytes so the optional bucket-minimum table that
-// follows them is aligned)
-inline size_t exec_lds_bytes(uint32_t cap, uint32_t agg_nb = 0) {
-  return exec_lds_runs_bytes(cap) + (agg_nb ? (size_t)(agg_nb + 1) * 4 : 0);
-}
-constexpr uint32_t kPersistRounds = 128;  // rounds per persistent launch (then a host sync)
-constexpr uint64_t kTimeEvery = 8;        // per-round launches: one timed in kTimeEvery
-
-}  // namespace
-
-
-namespace {
-
-// the round kernels of the simulation's traffic kind (k_execute: traced or lean)
-template <bool kTrace>
-const void* execute_fn_t(uint32_t kind) {
-  if (kind == SGN_TRAFFIC_TGEN) return (const void*)k_execute<kTrace, SGN_TRAFFIC_TGEN>;
-  if (kind == SGN_TRAFFIC_EXTERNAL) return (const void*)k_execute<kTrace, SGN_TRAFFIC_EXTERNAL>;
-  return (const void*)k_execute<kTrace, SGN_TRAFFIC_PERIODIC>;
-}
-const void* execute_fn(uint32_t kind, bool trace) {
-  return trace ? execute_fn_t<true>(kind) : execute_fn_t<false>(kind);
-}
-// (the twin with the diagnostics when the simulation starts with SGN_STAMPS set)
-bool rounds_diag() { return getenv("SGN_STAMPS") != nullptr; }
-template <bool kBig>
-const void* rounds_fn_t(uint32_t kind) {
-  if (rounds_diag()) {
-    if (kind == SGN_TRAFFIC_TGEN) return (const void*)k_rounds_diag<SGN_TRAFFIC_TGEN, kBig>;
-    if (kind == SGN_TRAFFIC_EXTERNAL) return (const void*)k_rounds_diag<SGN_TRAFFIC_EXTERNAL, kBig>;
-    return (const void*)k_rounds_diag<SGN_TRAFFIC_PERIODIC, kBig>;
-  }
-  if (kind == SGN_TRAFFIC_TGEN) return (const void*)k_rounds<SGN_TRAFFIC_TGEN, kBig>;
-  if (kind == SGN_TRAFFIC_EXTERNAL) return (const void*)k_rounds<SGN_TRAFFIC_EXTERNAL, kBig>;
-  return (const void*)k_rounds<SGN_TRAFFIC_PERIODIC, kBig>;
-}
-// the persistent kernel with the big-slab path only while a slab can hold more than CAP runs
-bool rounds_big(const sgn_ctx* ctx) { return ctx->ext_slabs > 0; }
-const void* rounds_fn(uint32_t kind, bool big) { return big ? rounds_fn_t<true>(kind) : rounds_fn_t<false>(kind); }
-template <bool kTrace>
-void launch_k_execute_t(sgn_ctx* ctx, hipStream_t st) {
-  const uint32_t k = ctx->S.tkind;
-  const dim3 grid(ctx->S.G), block(64);
-  const size_t lds = exec_lds_bytes(ctx->S.CAP, ctx->S.agg_bmin ? ctx->S.NB : 0);
-  const DevSim* d = (const DevSim*)ctx->d_S;
-  if (k == SGN_TRAFFIC_TGEN)
-    hipLaunchKernelGGL((k_execute<kTrace, SGN_TRAFFIC_TGEN>), grid, block, lds, st, d);
-  else if (k == SGN_TRAFFIC_EXTERNAL)
-    hipLaunchKernelGGL((k_execute<kTrace, SGN_TRAFFIC_EXTERNAL>), grid, block, lds, st, d);
-  else
-    hipLaunchKernelGGL((k_execute<kTrace, SGN_TRAFFIC_PERIODIC>), grid, block, lds, st, d);
-}
-void launch_k_execute(sgn_ctx* ctx, hipStream_t st) {
-  if (ctx->S.trace_on)
-    launch_k_execute_t<true>(ctx, st);
-  else
-    launch_k_execute_t<false>(ctx, st);
-}
-template <bool kBig>
-void launch_k_rounds_t(sgn_ctx* ctx, uint32_t n) {
-  const uint32_t k = ctx->S.tkind;
-  const dim3 grid(ctx->persist_grid), block(64);
-  const size_t lds = exec_lds_bytes(ctx->S.CAP, ctx->S.agg_bmin ? ctx->S.NB : 0);
-  const DevSim* d = (const DevSim*)ctx->d_S;
-  // (the census: this launch's epoch, and the arrivals of the launches before it)
-  const uint32_t ep = ++ctx->res_epoch, base = ctx->res_base;
-  ctx->res_base += ctx->persist_grid;
-  if (ctx->S.stamps) {  // (SGN_STAMPS at sgn_sim_init: the twin that writes them)
-    if (k == SGN_TRAFFIC_TGEN)
-      hipLaunchKernelGGL((k_rounds_diag<SGN_TRAFFIC_TGEN, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
-    else if (k == SGN_TRAFFIC_EXTERNAL)
-      hipLaunchKernelGGL((k_rounds_diag<SGN_TRAFFIC_EXTERNAL, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
-    else
-      hipLaunchKernelGGL((k_rounds_diag<SGN_TRAFFIC_PERIODIC, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
-    return;
-  }
-  if (k == SGN_TRAFFIC_TGEN)
-    hipLaunchKernelGGL((k_rounds<SGN_TRAFFIC_TGEN, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
-  else if (k == SGN_TRAFFIC_EXTERNAL)
-    hipLaunchKernelGGL((k_rounds<SGN_TRAFFIC_EXTERNAL, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
-  else
-    hipLaunchKernelGGL((k_rounds<SGN_TRAFFIC_PERIODIC, kBig>), grid, block, lds, ctx->stream, d, n, ep, base);
-}
-// the census verdict of the last persistent launch: 1 resident, 2 not (0: none recorded)
-uint32_t census_verdict(const sgn_ctx* ctx, uint32_t epoch) {
-  const uint32_t v = ctx->h_ctrl->res_verdict;
-  return (v >> 2) == (epoch & 0x3FFFFFFFu) ? (v & 3u) : 0u;
-}
-void launch_k_rounds(sgn_ctx* ctx, uint32_t n) {
-  if (rounds_big(ctx))
-    launch_k_rounds_t<true>(ctx, n);
-  else
-    launch_k_rounds_t<false>(ctx, n);
-}
-
-int launch_round(sgn_ctx* ctx) {
-  // a multi-shard round needs its exchange transport before anything is launched
-  if (ctx->nranks > 1 && !ctx->comm)
-    return set_error(ctx, SGN_ESTATE, "multi-shard round without an RCCL communicator");
-  hipStream_t st = ctx->stream;
-  // per-round launches time one round in kTimeEvery: an event record is a barrier packet
-  // with a cache write-back, and around every launch it cost 20 % of the rounds (eager) or
-  // 45 % (graph batches) on config C; a sample gives the kernel's average duration
-  const bool timed = ctx->capturing || (ctx->t_seq++ % kTimeEvery) == 0;
-  if (timed) time_begin(ctx, K_EXECUTE);
-  launch_k_execute(ctx, st);
-  if (timed) time_end(ctx);
-  if (!ctx->capturing) ctx->kt[K_EXECUTE].total++;
-  if (ctx->nranks > 1) {
-    // exchange + import + local finalize + all-reduce(min) + advance (comm.cpp)
-    int rc = comm_round_exchange(ctx);
-    if (rc) return rc;
-  } else {
-    // single shard: k_execute's last wave runs the round edge (finalize_fused)
-  }
-  SGN_HIP(ctx, hipGetLastError());
-  ctx->rounds_enqueued++;
-  return 0;
-}
-
-// Resident workgroups of a round kernel on this GPU (0: unknown): the occupancy query,
-// capped by LDS per CU (the device attribute: 160 KiB on gfx950) — LDS is allocated per
-// workgroup in 512-byte granules (a 23184-byte workgroup fits 6 per CU, not 7: a grid sized
-// for 7 was not resident and its barrier timed out)
-uint64_t resident_wg(sgn_ctx* ctx, const void* fn, size_t dyn) {
-  int occ = 0, ncu = 0, lds_cu = 0;
-  hipFuncAttributes fa{};
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64, dyn) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess ||
-      hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, ctx->device) != hipSuccess ||
-      hipFuncGetAttributes(&fa, fn) != hipSuccess || occ <= 0 || ncu <= 0 || lds_cu <= 0)
-    return 0;
-  const size_t lds_wg = (fa.sharedSizeBytes + dyn + 511) / 512 * 512;
-  ctx->lds_per_cu = (uint32_t)lds_cu;
-  return (uint64_t)std::min<int>(occ, (int)((size_t)lds_cu / lds_wg)) * (uint64_t)ncu;
-}
-
-// The largest slab capacity whose round-kernel LDS fits one workgroup (calendar re-layout).
-uint32_t max_slab_capacity(sgn_ctx* ctx, const DevSim& S) {
-  int per_block = 0;
-  if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess ||
-      per_block <= 0)
-    per_block = 64 * 1024;
-  size_t st = 0;
-  for (const void* fn : {rounds_fn(S.tkind, false), rounds_fn(S.tkind, true), execute_fn(S.tkind, S.trace_on)}) {
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, fn) == hipSuccess) st = std::max<size_t>(st, fa.sharedSizeBytes);
-  }
-  uint32_t cap = CAP_MIN;
-  while (cap < (1u << 15) && st + exec_lds_bytes(cap * 2, S.NB) <= (size_t)per_block) cap *= 2;
-  // test hook: a lower limit, so that hot slabs take extensions and the big-slab path at small sizes
-  if (const char* e = getenv("SGN_SLAB_LIM")) cap = std::max<uint32_t>(16, std::min<uint32_t>(cap, (uint32_t)atoi(e)));
-  return cap;
-}
-
-// The round kernels' shapes for the calendar as it is now (sim_init, and after a re-layout):
-// the LDS table of bucket minima ((NB + 1) x 4 bytes per workgroup, flush_bmin) is used when
-// it costs no resident workgroups where they count — the round kernels' grids stay as large
-// (config C has no LDS to spare: its 1563 groups need 7 workgroups per CU), or the grid
-// exceeds the chip either way (config D); SGN_AGG_BMIN=0/1 overrides — and the persistent
-// grid (single shard): entirely resident, with workgroups looping over groups when G exceeds
-// it. Persistent rounds keep the bucket -> slab table in LDS (each workgroup applies the
-// round's swap itself), so they need NB <= LDS_BSLAB; longer calendars run one launch per
-// round, and so does a traced run (k_rounds is built without the per-packet trace).
-void size_round_kernels(sgn_ctx* ctx, DevSim& S) {
-  const uint64_t G = S.G, NB = S.NB;
-  bool agg = S.tkind == SGN_TRAFFIC_PERIODIC;  // the kernels fold in LDS for PERIODIC traffic (kAggBmin)
-  for (const void* fn : {rounds_fn(S.tkind, false), rounds_fn(S.tkind, true), execute_fn(S.tkind, S.trace_on)}) {
-    const uint64_t r0 = resident_wg(ctx, fn, exec_lds_bytes(S.CAP)), r1 = resident_wg(ctx, fn, exec_lds_bytes(S.CAP, S.NB));
-    if (!r0 || std::min<uint64_t>(G, r1) < std::min<uint64_t>(G, r0)) agg = false;
-  }
-  if (const char* e = getenv("SGN_AGG_BMIN")) agg = atoi(e) != 0;
-  if ((NB + 1) * S.BW >= (1ULL << 32)) agg = false;  // offsets from the window start must fit u32
-  S.agg_bmin = agg ? 1u : 0u;
-  ctx->persist_grid = 0;
-  if (ctx->nranks == 1 && NB <= LDS_BSLAB && !S.trace_on && !ctx->persist_off &&
-      !(getenv("SGN_PERSISTENT") && atoi(getenv("SGN_PERSISTENT")) == 0)) {
-    // (resident for either variant: a re-layout that adds slab extensions switches to kBig)
-    const size_t lds = exec_lds_bytes(S.CAP, S.agg_bmin ? S.NB : 0);
-    const uint64_t res = std::min(resident_wg(ctx, rounds_fn(S.tkind, false), lds), resident_wg(ctx, rounds_fn(S.tkind, true), lds));
-    if (res) {
-      ctx->persist_grid = (uint32_t)std::min<uint64_t>(G, res);
-      // test hook: a smaller grid makes every workgroup serve several groups per round
-      if (const char* e = getenv("SGN_PERSIST_GRID"))
-        ctx->persist_grid = std::max<uint32_t>(1, std::min<uint32_t>(ctx->persist_grid, (uint32_t)atoi(e)));
-      // test hook: an oversized grid (not resident) exercises the residency census fallback
-      if (const char* e = getenv("SGN_PERSIST_GRID_FORCE")) ctx->persist_grid = (uint32_t)atoi(e);
-    }
-  }
-  if (ctx->persist_grid > 64 * RB_CH) ctx->persist_grid = 64 * RB_CH;
-}
-
-int check_overflow(sgn_ctx* ctx) {
-  const Ctrl& c = *ctx->h_ctrl;
-  if (c.overflow == 0) return 0;
-  std::string what;
-  if (c.overflow & OVF_BUCKET) what += " calendar bucket (raise sgn_sim_config.event_capacity)";
-  if (c.overflow & OVF_CODEL) what += " CoDel page pool (raise sgn_sim_config.codel_cap)";
-  if (c.overflow & OVF_SEG) what += " due-event segment buffer";
-  if (c.overflow & OVF_EXCHANGE) what += " exchange slot (raise exchange_slot_events)";
-  if (c.overflow & OVF_TRACE) what += " trace buffer";
-  if (c.overflow & OVF_TIMEOUT) what += " persistent grid barrier timed out (grid not resident)";
-  if (c.overflow & OVF_HORIZON) what += " event calendar horizon (a delivery beyond the calendar's buckets)";
-  if (c.overflow & OVF_DRAIN) what += " drain buffer (raise sgn_drain_enable's capacity or drain more often)";
-  return set_error(ctx, SGN_EOVERFLOW,
-                   "device capacity exceeded:" + what + " (info " +
-                       std::to_string(c.overflow_info) + "); results are invalid");
-}
-
-int sync_ctrl(sgn_ctx* ctx) {
-  if (!ctx->failed.empty()) return set_error(ctx, SGN_ESTATE, "simulation unusable: " + ctx->failed);
-  SGN_HIP(ctx, hipMemcpyAsync(ctx->h_ctrl, ctx->S.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost,
-                              ctx->stream));
-  SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  time_collect(ctx);
-  return check_overflow(ctx);
-}
-// After a persistent launch of census epoch ep: its own copy of the control block when it wrote
-// one (no device-to-host copy on the launch edge), else sync_ctrl.
-int sync_ctrl_persist(sgn_ctx* ctx, uint32_t ep) {
-  if (!ctx->failed.empty()) return set_error(ctx, SGN_ESTATE, "simulation unusable: " + ctx->failed);
-  if (!ctx->h_mirror) return sync_ctrl(ctx);
-  SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  constexpr size_t NW = sizeof(Ctrl) / 8;
-  if (__atomic_load_n(&ctx->h_mirror[NW], __ATOMIC_ACQUIRE) != ep || ctx->h_mirror[kMirrorWords - 1])
-    return sync_ctrl(ctx);
-  std::memcpy(ctx->h_ctrl, ctx->h_mirror, sizeof(Ctrl));
-  time_collect(ctx);
-  return check_overflow(ctx);
-}
-
-// ---- pools that grow (the reference's queues are unbounded): run at a held round edge ----
-int upload_sim(sgn_ctx* ctx) {
-  SGN_HIP(ctx, hipMemcpy(ctx->d_S, &ctx->S, sizeof(DevSim), hipMemcpyHostToDevice));
-  drop_graph(ctx);  // captured batches hold k_import's by-value DevSim
-  return 0;
-}
-
-// The calendar re-laid out after runs went past their slabs (a held round edge, or sgn_submit).
-// The slab capacity CAP doubles while more than 1/256 of the slabs (and more than 16) would
-// still overflow, up to what one workgroup's LDS orders at once; the few hot slabs past it get
-// extensions of 1.5x their fill (a slab keeps the capacity it had). Every run moves into the
-// new layout, the spilled runs after them; the spill area empties, and grows when it was more
-// than a quarter full. Device memory grows with the hot slabs only (sizing every
-// slab for the fullest cost config D ~8 -> ~16 GB for one hot slab).
-int relayout_calendar(sgn_ctx* ctx) {
-  DevSim& S = ctx->S;
-  Ctrl& c = *ctx->h_ctrl;
-  const uint64_t n_slabs = (uint64_t)(S.NB + 1) * S.G;
-  if (c.spill_n > S.spill_cap)
-    return set_error(ctx, SGN_EOVERFLOW, "calendar spill area exhausted within one round (" +
-                                             std::to_string(c.spill_n) + " runs, capacity " +
-                                             std::to_string(S.spill_cap) + ")");
-  const uint64_t nsp = c.spill_n;
-  std::vector<uint32_t> fill(n_slabs);
-  SGN_HIP(ctx, hipMemcpy(fill.data(), (const void*)S.slab_n, n_slabs * 4, hipMemcpyDeviceToHost));
-  const std::vector<uint64_t>& oext = ctx->h_ext;  // (empty: no extensions yet)
-  auto oecap = [&](uint64_t i) -> uint64_t { return oext.empty() ? 0 : oext[i] >> 40; };
-  // the new slab capacity
-  const uint32_t lim = std::max(S.CAP, max_slab_capacity(ctx, S));
-  const uint64_t few = std::max<uint64_t>(16, n_slabs / 256);
-  uint32_t cap = S.CAP;
-  size_t mfree = 0, mtot = 0;
-  if (hipMemGetInfo(&mfree, &mtot) != hipSuccess) mfree = 0;
-  while (cap * 2 <= lim && n_slabs * cap * 2 * sizeof(EvRec) < mfree / 2) {
-    uint64_t over = 0;
-    for (uint64_t i = 0; i < n_slabs; i++) over += fill[i] > cap;
-    if (over <= few) break;
-    cap *= 2;
-  }
-  // extensions: hot slabs keep room for 1.5x their fill, and never less than they had
-  std::vector<uint64_t> next(n_slabs, 0), hot_old;
-  uint64_t etot = 0, nhot = 0, max_oecap = 0;
-  for (uint64_t i = 0; i < n_slabs; i++) {
-    const uint64_t had = oecap(i) ? S.CAP + oecap(i) : 0;
-    if (oecap(i)) {
-      hot_old.push_back(i);
-      max_oecap = std::max(max_oecap, oecap(i));
-    }
-    // (a slab that fits the slab capacity or what it had keeps that; one that outgrew both gets
-    // 1.5x its fill — growth follows the fill, not the number of re-layouts)
-    const uint64_t need = fill[i] <= std::max<uint64_t>(had, cap) ? had : fill[i] + fill[i] / 2;
-    if (need <= cap) continue;
-    const uint64_t e = ((need - cap) + 63) / 64 * 64;
-    if (e >= (1ULL << 24))
-      return set_error(ctx, SGN_EOVERFLOW, "a calendar slab above 2^24 runs (slab " + std::to_string(i) + ", fill " +
-                                               std::to_string(fill[i]) + ", had " + std::to_string(had) + ", cap " +
-                                               std::to_string(S.CAP) + " -> " + std::to_string(cap) + ")");
-    next[i] = etot | (e << 40);
-    etot += e;
-    nhot++;
-  }
-  if (etot >= (1ULL << 40)) return set_error(ctx, SGN_EOVERFLOW, "calendar extensions above 2^40 runs");
-  const bool changed = cap != S.CAP || next != (oext.empty() ? std::vector<uint64_t>(n_slabs, 0) : oext);
-  if (changed) {
-    EvRec* np = cap != S.CAP ? (EvRec*)dev_alloc(ctx, n_slabs * cap * sizeof(EvRec), false) : (EvRec*)S.pool;
-    EvRec* nep = etot ? (EvRec*)dev_alloc(ctx, etot * sizeof(EvRec), false) : nullptr;
-    uint64_t* nxt = etot ? (uint64_t*)dev_alloc(ctx, n_slabs * 8, false) : nullptr;
-    uint32_t* cur = (uint32_t*)dev_alloc(ctx, (n_slabs + 1) * 4, false);  // + k_respill's lost-run count
-    uint64_t* dhot = hot_old.empty() ? nullptr : (uint64_t*)dev_alloc(ctx, hot_old.size() * 8, false);
-    auto undo = [&]() {
-      if (np && np != (EvRec*)S.pool) dev_free(ctx, np, n_slabs * cap * sizeof(EvRec));
-      if (nep) dev_free(ctx, nep, etot * sizeof(EvRec));
-      if (nxt) dev_free(ctx, nxt, n_slabs * 8);
-      if (cur) dev_free(ctx, cur, (n_slabs + 1) * 4);
-      if (dhot) dev_free(ctx, dhot, hot_old.size() * 8);
-    };
-    if (!np || (etot && (!nep || !nxt)) || !cur || (!hot_old.empty() && !dhot)) {
-      undo();
-      return set_error(ctx, SGN_ENOMEM, "device allocation failed (calendar re-layout)");
-    }
-    if (nxt) SGN_HIP(ctx, hipMemcpy(nxt, next.data(), n_slabs * 8, hipMemcpyHostToDevice));
-    if (dhot) SGN_HIP(ctx, hipMemcpy(dhot, hot_old.data(), hot_old.size() * 8, hipMemcpyHostToDevice));
-    SGN_HIP(ctx, hipMemsetAsync(cur + n_slabs, 0, 4, ctx->stream));
-    // the pool part moves only when the slabs grow (in place it stays where it is)
-    const uint64_t nt = n_slabs * S.CAP;
-    if (np != (EvRec*)S.pool) {
-      hipLaunchKernelGGL(k_relayout, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, ctx->stream,
-                         (const EvRec*)S.pool, S.CAP, (const uint64_t*)S.ext, np, cap, (const uint64_t*)nxt, nep,
-                         (const uint32_t*)S.slab_n, cur, n_slabs);
-    } else {
-      std::vector<uint32_t> hc(n_slabs);
-      for (uint64_t i = 0; i < n_slabs; i++) hc[i] = (uint32_t)std::min<uint64_t>(fill[i], S.CAP + oecap(i));
-      SGN_HIP(ctx, hipMemcpy(cur, hc.data(), n_slabs * 4, hipMemcpyHostToDevice));
-    }
-    if (!hot_old.empty()) {
-      const uint64_t ne = hot_old.size() * max_oecap;
-      hipLaunchKernelGGL(k_relayout_ext, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
-                         (const uint64_t*)dhot, (uint64_t)hot_old.size(), (uint32_t)max_oecap,
-                         (const EvRec*)S.ext_pool, (const uint64_t*)S.ext, S.CAP, np, cap, (const uint64_t*)nxt, nep,
-                         (const uint32_t*)S.slab_n);
-    }
-    if (nsp)
-      hipLaunchKernelGGL(k_respill, dim3((uint32_t)((nsp + 255) / 256)), dim3(256), 0, ctx->stream,
-                         (const EvRec*)S.spill, (const uint32_t*)S.spill_idx, nsp, np, cap, (const uint64_t*)nxt,
-                         nep, cur, cur + n_slabs);
-    SGN_HIP(ctx, hipGetLastError());
-    SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    uint32_t lost = 0;
-    SGN_HIP(ctx, hipMemcpy(&lost, cur + n_slabs, 4, hipMemcpyDeviceToHost));
-    if (lost) {
-      ctx->failed = "calendar re-layout lost " + std::to_string(lost) + " spilled runs (slab sizing)";
-      return set_error(ctx, SGN_EOVERFLOW, ctx->failed);
-    }
-    if (np != (EvRec*)S.pool) dev_free(ctx, (void*)S.pool, n_slabs * S.CAP * sizeof(EvRec));
-    if (S.ext_pool) dev_free(ctx, (void*)S.ext_pool, S.ext_total * sizeof(EvRec));
-    if (S.ext) dev_free(ctx, (void*)S.ext, n_slabs * 8);
-    dev_free(ctx, cur, (n_slabs + 1) * 4);
-    if (dhot) dev_free(ctx, dhot, hot_old.size() * 8);
-    if (cap != S.CAP) ctx->cal_grows++;
-    S.pool = (decltype(S.pool))np;
-    S.CAP = cap;
-    S.ext = (decltype(S.ext))nxt;
-    S.ext_pool = (decltype(S.ext_pool))nep;
-    S.ext_total = etot;
-    ctx->h_ext = etot ? next : std::vector<uint64_t>();
-    ctx->ext_slabs = nhot;
-    S.gspec = std::min<uint32_t>(S.gspec, S.CAP);
-    size_round_kernels(ctx, S);
-  }
-  ctx->cal_spill_runs += nsp;
-  // the spill area: emptied; grown when this round used more than a quarter of it
-  if (nsp > S.spill_cap / 4) {
-    const uint64_t ncap = std::min<uint64_t>(1ULL << 30, std::max<uint64_t>(2 * S.spill_cap, 4 * nsp));
-    EvRec* sp = (EvRec*)dev_alloc(ctx, ncap * sizeof(EvRec), false);
-    uint32_t* si = (uint32_t*)dev_alloc(ctx, ncap * 4, false);
-    if (sp && si) {
-      dev_free(ctx, (void*)S.spill, S.spill_cap * sizeof(EvRec));
-      dev_free(ctx, (void*)S.spill_idx, S.spill_cap * 4);
-      S.spill = (decltype(S.spill))sp;
-      S.spill_idx = (decltype(S.spill_idx))si;
-      S.spill_cap = ncap;
-      ctx->spill_grows++;
-    } else {  // (the area as it was still works)
-      if (sp) dev_free(ctx, sp, ncap * sizeof(EvRec));
-      if (si) dev_free(ctx, si, ncap * 4);
-    }
-  }
-  const uint64_t zero[2] = {0, 0};
-  SGN_HIP(ctx, hipMemcpy((char*)S.ctrl + offsetof(Ctrl, spill_n), zero, 8, hipMemcpyHostToDevice));
-  SGN_HIP(ctx, hipMemcpy((char*)S.ctrl + offsetof(Ctrl, spill_imp), zero, 8, hipMemcpyHostToDevice));
-  c.spill_n = 0;
-  c.spill_imp = 0;
-  return upload_sim(ctx);
-}
-
-// the CoDel pages the round of the current window may take (codel_round_bound, host form)
-uint64_t codel_need_host(const sgn_ctx* ctx) {
-  const DevSim& S = ctx->S;
-  const Ctrl& c = *ctx->h_ctrl;
-  if (!c.active || c.we <= c.ws) return 0;
-  auto bk = [&](uint64_t t) { return (uint32_t)((t - SIM_START) / S.BW) & (S.NB - 1); };
-  const uint64_t nbk = ((bk(c.we - 1) - bk(c.ws)) & (S.NB - 1)) + 1;
-  return codel_pages_bound(std::min<uint64_t>(c.cal_occ, nbk * S.G * S.CAP + S.ext_total), S.nH);
-}
-
-// A CoDel page pool with at least `extra` more free pages (and at least double the size): the
-// pages keep their indices (host records and chains stay valid), the free ring is rebuilt as
-// its current entries followed by the new pages.
-int grow_codel(sgn_ctx* ctx, uint64_t extra) {
-  DevSim& S = ctx->S;
-  Ctrl& c = *ctx->h_ctrl;
-  if (c.pg_avail != c.pg_tail)
-    return set_error(ctx, SGN_ESTATE, "CoDel pool growth outside a round edge");
-  const uint64_t P = S.cq_pages;
-  const uint64_t P2 = std::max<uint64_t>(2 * P, P + extra + extra / 2 + 64);
-  if (P2 >= (1ULL << 28)) return set_error(ctx, SGN_EOVERFLOW, "CoDel page pool above 2^28 pages");
-  CodelEnt* ne = (CodelEnt*)dev_alloc(ctx, P2 * CQ_PAGE * sizeof(CodelEnt), false);
-  uint32_t* nn = (uint32_t*)dev_alloc(ctx, P2 * 4, true);
-  uint32_t* nf = (uint32_t*)dev_alloc(ctx, P2 * 4, false);
-  if (!ne || !nn || !nf) return set_error(ctx, SGN_ENOMEM, "device allocation failed (CoDel pool growth)");
-  SGN_HIP(ctx, hipMemcpy(ne, (const void*)S.codel, P * CQ_PAGE * sizeof(CodelEnt), hipMemcpyDeviceToDevice));
-  SGN_HIP(ctx, hipMemcpy(nn, (const void*)S.cq_next, P * 4, hipMemcpyDeviceToDevice));
-  std::vector<uint32_t> ring(P), fr;
-  SGN_HIP(ctx, hipMemcpy(ring.data(), (const void*)S.cq_free, P * 4, hipMemcpyDeviceToHost));
-  fr.reserve(P2);
-  for (uint64_t i = c.pg_alloc; i < c.pg_tail; i++) fr.push_back(ring[i % P]);
-  for (uint64_t pg = P; pg < P2; pg++) fr.push_back((uint32_t)pg);
-  const uint64_t nfree = fr.size();
-  fr.resize(P2, 0);
-  SGN_HIP(ctx, hipMemcpy(nf, fr.data(), P2 * 4, hipMemcpyHostToDevice));
-  dev_free(ctx, (void*)S.codel, P * CQ_PAGE * sizeof(CodelEnt));
-  dev_free(ctx, (void*)S.cq_next, P * 4);
-  dev_free(ctx, (void*)S.cq_free, P * 4);
-  S.codel = (decltype(S.codel))ne;
-  S.cq_next = (decltype(S.cq_next))nn;
-  S.cq_free = (decltype(S.cq_free))nf;
-  S.cq_pages = (uint32_t)P2;
-  S.div_cq.init(P2);
-  ctx->codel_allocs_before += c.pg_alloc;
-  c.pg_alloc = 0;
-  c.pg_tail = c.pg_avail = nfree;
-  SGN_HIP(ctx, hipMemcpy((char*)S.ctrl + offsetof(Ctrl, pg_alloc), &c.pg_alloc, 3 * 8, hipMemcpyHostToDevice));
-  ctx->codel_grows++;
-  return upload_sim(ctx);
-}
-
-// Multi-shard: a round in which some shard had more runs for a peer than a slot holds (the
-// messages carry every shard's largest count, so every shard grows alike to twice that):
-// the slots grow, keeping each outgoing block's message and runs, and the runs that went to
-// the spill area (tagged SPILL_PEER | peer) follow them; comm_complete_spill then moves the
-// whole slots and completes the round.
-int grow_exchange_slot_impl(sgn_ctx* ctx) {
-  DevSim& S = ctx->S;
-  const uint64_t hwm = ctx->h_ctrl->xhwm;
-  uint64_t ns = S.xslot;
-  while (ns < 2 * hwm) ns *= 2;
-  if (ns > (1ULL << 26)) return set_error(ctx, SGN_EOVERFLOW, "exchange slot above 2^26 runs per peer");
-  const size_t ob = XHDR + (size_t)S.xslot, nb = XHDR + (size_t)ns, R = S.n_ranks;
-  EvRec* nxo = (EvRec*)dev_alloc(ctx, R * nb * sizeof(EvRec), true);
-  EvRec* nxi = (EvRec*)dev_alloc(ctx, R * nb * sizeof(EvRec), true);
-  if (!nxo || !nxi) return set_error(ctx, SGN_ENOMEM, "device allocation failed (exchange slot growth)");
-  // (xin too: this shard's own message sits in its incoming block)
-  for (size_t p = 0; p < R; p++) {
-    SGN_HIP(ctx, hipMemcpy(nxo + p * nb, (const void*)(S.xout + p * ob), ob * sizeof(EvRec), hipMemcpyDeviceToDevice));
-    SGN_HIP(ctx, hipMemcpy(nxi + p * nb, (const void*)(S.xin + p * ob), ob * sizeof(EvRec), hipMemcpyDeviceToDevice));
-  }
-  const uint64_t n = std::min<uint64_t>(ctx->h_ctrl->spill_n, S.spill_cap);
-  if (n) {
-    std::vector<uint32_t> idx(n);
-    std::vector<EvRec> rec(n);
-    SGN_HIP(ctx, hipMemcpy(idx.data(), (const void*)S.spill_idx, n * 4, hipMemcpyDeviceToHost));
-    SGN_HIP(ctx, hipMemcpy(rec.data(), (const void*)S.spill, n * sizeof(EvRec), hipMemcpyDeviceToHost));
-    std::vector<std::vector<EvRec>> per(R);
-    for (uint64_t i = 0; i < n; i++)
-      if ((idx[i] & SPILL_PEER) && idx[i] != SPILL_DEAD) per[idx[i] & ~SPILL_PEER].push_back(rec[i]);
-    for (size_t p = 0; p < R; p++)
-      if (!per[p].empty())
-        SGN_HIP(ctx, hipMemcpy(nxo + p * nb + ob, per[p].data(), per[p].size() * sizeof(EvRec), hipMemcpyHostToDevice));
-  }
-  dev_free(ctx, (void*)S.xout, R * ob * sizeof(EvRec));
-  dev_free(ctx, (void*)S.xin, R * ob * sizeof(EvRec));
-  S.xout = (decltype(S.xout))nxo;
-  S.xin = (decltype(S.xin))nxi;
-  S.xslot = (uint32_t)ns;
-  ctx->xslot = ns;
-  ctx->xslot_grows++;
-  if (int rc = xpeer_upload(ctx)) return rc;  // (the send blocks moved)
-  return upload_sim(ctx);
-}
-
-// A round edge held the rounds (Ctrl::hold; nothing of the next round has run): the calendar
-// is re-laid out after a spill, the CoDel pool grows until its free pages cover the next
-// round's bound, and the rounds are released. (Multi-shard: every shard holds the same round;
-// each grows what it needs.)
-int resolve_hold(sgn_ctx* ctx) {
-  Ctrl& c = *ctx->h_ctrl;
-  if (!c.hold) {
-    // (multi-shard: runs k_import spilled hold nothing; re-laid out at the batch's sync)
-    return c.spill_n ? relayout_calendar(ctx) : 0;
-  }
-  int rc = 0;
-  if (c.spill_n && (rc = relayout_calendar(ctx))) return rc;
-  // (the bound again for the layout as it is now: spilled runs may be due in the held round)
-  const uint64_t need = std::max(c.hold_need, codel_need_host(ctx));
-  const uint64_t free = c.pg_avail > c.pg_alloc ? c.pg_avail - c.pg_alloc : 0;
-  // (a pause is sgn_run_until's stop, not a pool's: it is released like one, but not counted,
-  // and alone it grows nothing — the run goes on exactly as one without the pause would)
-  if ((c.hold & ~HOLD_PAUSE) && free < need && (rc = grow_codel(ctx, need - free))) return rc;
-  if (c.hold & HOLD_PAUSE) ctx->paused = true;
-  if (c.hold & ~HOLD_PAUSE) ctx->rounds_held++;
-  c.hold = 0;
-  c.hold_need = 0;
-  SGN_HIP(ctx, hipMemcpy((char*)ctx->S.ctrl + offsetof(Ctrl, hold), &c.hold, 4, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// Event-record nodes around the timed kernel nodes of a captured batch (a captured
-// hipEventRecord yields no timing on ROCm 7.2; explicit record nodes do).
-int add_timing_nodes(sgn_ctx* ctx, hipGraph_t g) {
-  const bool all = ctx->flags & SGN_CREATE_TIME_KERNELS;
-  const bool exec = ctx->flags & SGN_CREATE_TIME_EXECUTE;
-  ctx->graph_timed.clear();
-  if (!all && !exec) return 0;
-  const void* fn[K_NUM] = {execute_fn(ctx->S.tkind, ctx->S.trace_on), (const void*)k_import};
-  size_t n = 0;
-  SGN_HIP(ctx, hipGraphGetNodes(g, nullptr, &n));
-  std::vector<hipGraphNode_t> nodes(n);
-  SGN_HIP(ctx, hipGraphGetNodes(g, nodes.data(), &n));
-  size_t ev = 0;
-  uint32_t tseen[K_NUM] = {};
-  for (hipGraphNode_t node : nodes) {
-    hipGraphNodeType t;
-    SGN_HIP(ctx, hipGraphNodeGetType(node, &t));
-    if (t != hipGraphNodeTypeKernel) continue;
-    hipKernelNodeParams p;
-    SGN_HIP(ctx, hipGraphKernelNodeGetParams(node, &p));
-    int kid = -1;
-    for (int k = 0; k < K_NUM; k++)
-      if (p.func == fn[k]) kid = k;
-    if (kid < 0 || (!all && kid != K_EXECUTE)) continue;
-    if ((tseen[kid]++ % kTimeEvery) != 0) continue;  // a sample (launch_round's note)
-    if (ev >= ctx->ev_pool.size()) {
-      hipEvent_t a, b;
-      SGN_HIP(ctx, hipEventCreate(&a));
-      SGN_HIP(ctx, hipEventCreate(&b));
-      ctx->ev_pool.push_back({a, b});
-    }
-    size_t nd = 0, nn = 0;
-    SGN_HIP(ctx, hipGraphNodeGetDependencies(node, nullptr, &nd));
-    std::vector<hipGraphNode_t> deps(nd);
-    if (nd) SGN_HIP(ctx, hipGraphNodeGetDependencies(node, deps.data(), &nd));
-    SGN_HIP(ctx, hipGraphNodeGetDependentNodes(node, nullptr, &nn));
-    std::vector<hipGraphNode_t> outs(nn);
-    if (nn) SGN_HIP(ctx, hipGraphNodeGetDependentNodes(node, outs.data(), &nn));
-    hipGraphNode_t a, b;
-    SGN_HIP(ctx, hipGraphAddEventRecordNode(&a, g, nd ? deps.data() : nullptr, nd, ctx->ev_pool[ev].first));
-    SGN_HIP(ctx, hipGraphAddDependencies(g, &a, &node, 1));
-    SGN_HIP(ctx, hipGraphAddEventRecordNode(&b, g, &node, 1, ctx->ev_pool[ev].second));
-    for (hipGraphNode_t o : outs) SGN_HIP(ctx, hipGraphAddDependencies(g, &b, &o, 1));
-    ctx->graph_timed.push_back({kid, ev});
-    ev++;
-  }
-  return 0;
-}
-
-}  // namespace
-
 namespace sgn {
 
-void time_begin(sgn_ctx* ctx, int kernel) {
-  if (ctx->capturing) return;  // graph mode: event-record nodes are added after capture
-  const bool all = ctx->flags & SGN_CREATE_TIME_KERNELS;
-  const bool exec = (ctx->flags & SGN_CREATE_TIME_EXECUTE) && kernel == K_EXECUTE;
-  if (!all && !exec) return;
-  if (ctx->ev_next >= ctx->ev_pool.size()) {
-    hipEvent_t a, b;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-    ctx->ev_pool.push_back({a, b});
-  }
-  hipEventRecord(ctx->ev_pool[ctx->ev_next].first, ctx->stream);
-  ctx->ev_pending.push_back({kernel, ctx->ev_next});
-}
-
-void time_end(sgn_ctx* ctx) {
-  if (ctx->capturing) return;
-  if (!(ctx->flags & (SGN_CREATE_TIME_KERNELS | SGN_CREATE_TIME_EXECUTE))) return;
-  if (ctx->ev_pending.empty() || ctx->ev_pending.back().second != ctx->ev_next) return;
-  hipEventRecord(ctx->ev_pool[ctx->ev_next].second, ctx->stream);
-  ctx->ev_next++;
-}
-
-void time_collect(sgn_ctx* ctx) {
-  if (!(ctx->flags & (SGN_CREATE_TIME_KERNELS | SGN_CREATE_TIME_EXECUTE))) return;
-  if (ctx->graph_pending) {
-    // events recorded by the replayed graph's event-record nodes
-    for (auto& p : ctx->graph_timed) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, ctx->ev_pool[p.second].first,
-                              ctx->ev_pool[p.second].second) == hipSuccess) {
-        ctx->kt[p.first].ms += ms;
-        ctx->kt[p.first].launches++;
-      }
-    }
-    ctx->graph_pending = false;
-  }
-  for (auto& p : ctx->ev_pending) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->ev_pool[p.second].first, ctx->ev_pool[p.second].second) ==
-        hipSuccess) {
-      ctx->kt[p.first].ms += ms;
-      ctx->kt[p.first].launches++;
-    }
-  }
-  ctx->ev_pending.clear();
-  ctx->ev_next = 0;
-}
-
-int ctrl_sync(sgn_ctx* ctx) { return sync_ctrl(ctx); }
-int grow_exchange_slot(sgn_ctx* ctx) { return grow_exchange_slot_impl(ctx); }
-int resolve_pools(sgn_ctx* ctx) { return resolve_hold(ctx); }
-int sim_upload(sgn_ctx* ctx) { return upload_sim(ctx); }
-void round_kernels_resize(sgn_ctx* ctx) { size_round_kernels(ctx, ctx->S); }
-
-void drop_graph(sgn_ctx* ctx) {
-  if (ctx->gexec) hipGraphExecDestroy(ctx->gexec);
-  if (ctx->graph) hipGraphDestroy(ctx->graph);
-  ctx->gexec = nullptr;
-  ctx->graph = nullptr;
-  ctx->gbatch = 0;
-  ctx->gsz = 0;
-  ctx->graph_timed.clear();
-  ctx->graph_pending = false;
-}
-
-// ---- persistent multi-shard rounds (k_rounds_x): host side ----
-// Inbox layout (one uncached allocation per shard): headers [2][R][XH_WORDS], census words [R]
-// (padded to a line), runs [2][R][xislot].
-// (then the bins: [2][R][G][xbk] runs, G = the receiving shard's host groups)
-XLay xlay(uint32_t R, uint64_t xislot, uint32_t G, uint32_t xbk) {
-  XLay l;
-  l.hdr = 0;
-  l.cen = (size_t)2 * R * XH_WORDS * 8;
-  l.runs = l.cen + ((size_t)R * 8 + 127) / 128 * 128;
-  l.bins = l.runs + (size_t)2 * R * xislot * sizeof(EvRec);
-  l.bytes = l.bins + (size_t)2 * R * G * xbk * sizeof(EvRec);
-  return l;
-}
-
-void xinbox_release(sgn_ctx* ctx) {
-  for (void* p : ctx->x_opened)
-    if (p) (void)hipIpcCloseMemHandle(p);
-  ctx->x_opened.clear();
-  if (ctx->xin_mem) {
-    (void)hipFree(ctx->xin_mem);
-    ctx->sim_bytes -= std::min<uint64_t>(ctx->sim_bytes, ctx->xin_bytes);
-  }
-  ctx->xin_mem = nullptr;
-  ctx->xin_bytes = 0;
-  ctx->x_base.clear();
-  ctx->x_mapped = false;
-}
-
-// A (new) inbox of xislot runs per sender and round parity, zeroed (no tag matches a round).
-// Uncached device memory: peers' stores reach it over xGMI and no L2 — the writer's or this
-// GPU's — keeps a copy, so the tags polled and the runs read here are the memory's. The old
-// inbox and the peer mappings go (the caller maps the new ones).
-int xinbox_alloc(sgn_ctx* ctx, uint64_t xislot) {
-  DevSim& S = ctx->S;
-  const XLay l = xlay(ctx->nranks, xislot, S.G, S.xbk);
-  void* p = nullptr;
-  // (a local group's shards share this GPU: ordinary device memory, device-scope accesses;
-  // one shard per GPU: uncached, the peers write it over xGMI)
-  S.xsys = ctx->comm_local ? 0u : 1u;
-  hipError_t e = S.xsys ? hipExtMallocWithFlags(&p, l.bytes, hipDeviceMallocUncached) : hipMalloc(&p, l.bytes);
-  if (e != hipSuccess) return set_error(ctx, SGN_ENOMEM, std::string("inbox allocation: ") + hipGetErrorString(e));
-  if ((e = hipMemset(p, 0, l.bytes)) != hipSuccess) {
-    (void)hipFree(p);
-    return hip_fail(ctx, e, "hipMemset (inbox)");
-  }
-  xinbox_release(ctx);
-  ctx->xin_mem = p;
-  ctx->xin_bytes = l.bytes;
-  ctx->sim_bytes += l.bytes;
-  S.xin_hdr = (decltype(S.xin_hdr))((char*)p + l.hdr);
-  S.xin_cen = (decltype(S.xin_cen))((char*)p + l.cen);
-  S.xin_runs = (decltype(S.xin_runs))((char*)p + l.runs);
-  S.xislot = (uint32_t)xislot;
-  S.xin_bins = S.xbk ? (decltype(S.xin_bins))((char*)p + l.bins) : nullptr;
-  return 0;
-}
-
-// This shard's XPeer table: its slot, header and census word in every shard's inbox
-// (ctx->x_base, by rank; none before the mapping) and the RCCL transport's send blocks.
-int xpeer_upload(sgn_ctx* ctx) {
-  DevSim& S = ctx->S;
-  const uint32_t R = ctx->nranks, s = ctx->rank;
-  std::vector<XPeer> xp(R);
-  std::memset(xp.data(), 0, R * sizeof(XPeer));
-  for (uint32_t q = 0; q < R; q++) {
-    XPeer& x = xp[q];
-    char* b = q < ctx->x_base.size() ? ctx->x_base[q] : nullptr;
-    const uint32_t Gq = q < ctx->x_G.size() ? ctx->x_G[q] : 0;
-    const XLay l = xlay(R, S.xislot, Gq, S.xbk);  // (receiver q's inbox)
-    if (b) {
-      for (uint32_t k = 0; k < 2; k++) {
-        x.runs[k] = (std::remove_reference_t<decltype(x.runs[k])>)((EvRec*)(b + l.runs) + ((size_t)k * R + s) * S.xislot);
-        x.hdr[k] = (std::remove_reference_t<decltype(x.hdr[k])>)((uint64_t*)(b + l.hdr) + ((size_t)k * R + s) * XH_WORDS);
-        if (S.xbk)
-          x.bins[k] = (std::remove_reference_t<decltype(x.bins[k])>)((EvRec*)(b + l.bins) + ((size_t)k * R + s) * Gq * S.xbk);
-      }
-      x.cen = (decltype(x.cen))((uint64_t*)(b + l.cen) + s);
-    }
-    if (S.xout) x.runs[2] = (std::remove_reference_t<decltype(x.runs[2])>)((EvRec*)S.xout + (size_t)q * (S.xslot + XHDR) + XHDR);
-  }
-  SGN_HIP(ctx, hipMemcpy(ctx->d_xp, xp.data(), R * sizeof(XPeer), hipMemcpyHostToDevice));
-  return 0;
-}
-
-// The persistent multi-shard path runs where the persistent kernel would (the bucket -> slab
-// table in LDS, no per-packet trace) unless refused before or switched off (SGN_XPERSIST=0 or
-// SGN_PERSISTENT=0: per-round launches and the RCCL / local-copy exchange).
-bool xpersist_possible(sgn_ctx* ctx) {
-  // (read per call, like the single-shard path's SGN_PERSISTENT: a test that changes either
-  // variable within one process must see it — ADVICE r5)
-  const bool off = (getenv("SGN_XPERSIST") && atoi(getenv("SGN_XPERSIST")) == 0) ||
-                   (getenv("SGN_PERSISTENT") && atoi(getenv("SGN_PERSISTENT")) == 0);
-  return ctx->nranks > 1 && ctx->nranks <= XR_MAX && ctx->sim_ready && ctx->xin_mem && ctx->S.NB <= LDS_BSLAB &&
-         !ctx->S.trace_on &&
-         !ctx->x_off && !ctx->persist_off && !off;
-}
-
-// runs into this shard's calendar at a held round edge (k_inject: the bucket's current slab)
-int inject_runs(sgn_ctx* ctx, const std::vector<EvRec>& runs) {
-  if (runs.empty()) return 0;
-  void* d = nullptr;
-  SGN_HIP(ctx, hipMalloc(&d, runs.size() * sizeof(EvRec)));
-  hipError_t e = hipMemcpy(d, runs.data(), runs.size() * sizeof(EvRec), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_inject, dim3((uint32_t)((runs.size() + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const DevSim*)ctx->d_S, (const EvRec*)d, (uint32_t)runs.size());
-    e = hipStreamSynchronize(ctx->stream);
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) return hip_fail(ctx, e, "inject_runs");
-  return 0;
-}
-
 namespace {
-const void* rounds_x_fn(uint32_t kind) {
-  if (kind == SGN_TRAFFIC_TGEN) return (const void*)k_rounds_x<SGN_TRAFFIC_TGEN>;
-  if (kind == SGN_TRAFFIC_EXTERNAL) return (const void*)k_rounds_x<SGN_TRAFFIC_EXTERNAL>;
-  return (const void*)k_rounds_x<SGN_TRAFFIC_PERIODIC>;
-}
-
-// One k_rounds_x launch of up to n rounds over the shards sh (all on sh[0]'s GPU and stream).
-// Returns 1 when no resident grid can be sized (the caller falls back to per-round launches).
-int x_launch(const std::vector<sgn_ctx*>& sh, bool peers, uint32_t n) {
-  sgn_ctx* c0 = sh[0];
-  const uint32_t kind = c0->S.tkind;
-  size_t lds = 0;
-  uint64_t sumG = 0;
-  for (sgn_ctx* c : sh) {
-    lds = std::max(lds, exec_lds_bytes(c->S.CAP, c->S.agg_bmin ? c->S.NB : 0));
-    sumG += c->S.G;
+// The table, by traffic kind (index 0 TGEN, 1 EXTERNAL, 2 PERIODIC). Filling it is what instantiates
+// the 21 templated round kernels, and the compiler emits them in the order they are first named:
+// the entries are written out in the order these names had in the launch ladders that stood here,
+// so the code object keeps its kernel order (profiles/r09 suspected code placement behind a 0.3 %
+// shift on config D).
+struct RoundKernelTable {
+  RoundKernels k[3];
+  RoundKernelTable() {
+    constexpr uint32_t T = SGN_TRAFFIC_TGEN, E = SGN_TRAFFIC_EXTERNAL, P = SGN_TRAFFIC_PERIODIC;
+    typedef const void* F;
+    k[0].execute[1] = (F)k_execute<true, T>, k[1].execute[1] = (F)k_execute<true, E>, k[2].execute[1] = (F)k_execute<true, P>;
+    k[0].execute[0] = (F)k_execute<false, T>, k[1].execute[0] = (F)k_execute<false, E>, k[2].execute[0] = (F)k_execute<false, P>;
+    k[0].rounds[1][1] = (F)k_rounds_diag<T, true>, k[1].rounds[1][1] = (F)k_rounds_diag<E, true>, k[2].rounds[1][1] = (F)k_rounds_diag<P, true>;
+    k[0].rounds[0][1] = (F)k_rounds<T, true>, k[1].rounds[0][1] = (F)k_rounds<E, true>, k[2].rounds[0][1] = (F)k_rounds<P, true>;
+    k[0].rounds[1][0] = (F)k_rounds_diag<T, false>, k[1].rounds[1][0] = (F)k_rounds_diag<E, false>, k[2].rounds[1][0] = (F)k_rounds_diag<P, false>;
+    k[0].rounds[0][0] = (F)k_rounds<T, false>, k[1].rounds[0][0] = (F)k_rounds<E, false>, k[2].rounds[0][0] = (F)k_rounds<P, false>;
+    k[0].rounds_x = (F)k_rounds_x<T>, k[1].rounds_x = (F)k_rounds_x<E>, k[2].rounds_x = (F)k_rounds_x<P>;
   }
-  const uint64_t res = resident_wg(c0, rounds_x_fn(kind), lds) / std::max<uint32_t>(1, peers ? c0->x_share : 1);
-  // A refusal is decided here, from this GPU's LDS and residency alone (CAP may differ between
-  // shards after their re-layouts). A local group falls back at once; one shard per GPU must not,
-  // or its peers would launch and wait for it: it launches ONE workgroup that publishes "not
-  // resident" to every peer's census word, and every shard falls back together.
-  bool refuse = !res || res < sh.size();
-  // (test hook: this rank refuses as if its GPU could not hold the grid)
-  if (peers && getenv("SGN_XREFUSE_RANK") && atoi(getenv("SGN_XREFUSE_RANK")) == (int)c0->rank) refuse = true;
-  if (refuse && !peers) return 1;
-  if (!c0->x_hxl) SGN_HIP(c0, hipHostMalloc(&c0->x_hxl, sizeof(XLaunch), 0));
-  XLaunch& xl = *(XLaunch*)c0->x_hxl;
-  std::memset(&xl, 0, sizeof(xl));
-  xl.n_local = (uint32_t)sh.size();
-  xl.peers_census = peers ? 1u : 0u;
-  xl.refuse = refuse ? 1u : 0u;
-  xl.epoch = ++c0->x_epoch;
-  uint32_t b = 0;
-  const char* cap_env = getenv("SGN_PERSIST_GRID");
-  for (size_t i = 0; i < sh.size(); i++) {
-    sgn_ctx* c = sh[i];
-    uint64_t P = std::max<uint64_t>(1, std::min<uint64_t>(c->S.G, res * c->S.G / sumG));
-    if (cap_env) P = std::max<uint64_t>(1, std::min<uint64_t>(P, (uint64_t)atoi(cap_env)));
-    P = std::min<uint64_t>(P, 64 * RB_CH);
-    if (refuse) P = 1;
-    xl.base[i] = b;
-    xl.S[i] = (std::remove_reference_t<decltype(xl.S[i])>)c->d_S;
-    b += (uint32_t)P;
-    c->x_grid = (uint32_t)P;
-    const DevSim& S = c->S;
-    (void)S;  // (no per-launch memsets: each shard's launch resets its round buffers itself)
-  }
-  xl.base[sh.size()] = b;
-  xl.res_base = c0->res_base;  // (the census counts in the first shard's control block)
-  if (!refuse) c0->res_base += b;  // (a refused launch runs no census)
-  if (refuse) lds = 0;             // (its one workgroup leaves before touching the dynamic LDS)
-  SGN_HIP(c0, hipMemcpyAsync(c0->d_xl, &xl, sizeof(XLaunch), hipMemcpyHostToDevice, c0->stream));
-  time_begin(c0, K_EXECUTE);
-  const dim3 grid(b), block(64);
-  const XLaunch* d = (const XLaunch*)c0->d_xl;
-  if (kind == SGN_TRAFFIC_TGEN)
-    hipLaunchKernelGGL((k_rounds_x<SGN_TRAFFIC_TGEN>), grid, block, lds, c0->stream, d, n);
-  else if (kind == SGN_TRAFFIC_EXTERNAL)
-    hipLaunchKernelGGL((k_rounds_x<SGN_TRAFFIC_EXTERNAL>), grid, block, lds, c0->stream, d, n);
-  else
-    hipLaunchKernelGGL((k_rounds_x<SGN_TRAFFIC_PERIODIC>), grid, block, lds, c0->stream, d, n);
-  time_end(c0);
-  c0->kt[K_EXECUTE].total++;
-  SGN_HIP(c0, hipGetLastError());
-  for (sgn_ctx* c : sh) {
-    c->x_launches++;
-    c->x_mode = 2;
-  }
-  return 0;
-}
-
-// A round edge held by k_rounds_x (every shard the same flags): runs past an inbox slot go from
-// the senders' spill areas into their shards' calendars, and the inboxes grow; then each shard's
-// own pools (resolve_hold). sh: every shard of the group (local) or this GPU's one (peers).
-int x_resolve(const std::vector<sgn_ctx*>& sh, bool peers) {
-  uint32_t hold = 0;
-  uint64_t hwm = 0;
-  for (sgn_ctx* c : sh) {
-    hold |= c->h_ctrl->hold;
-    hwm = std::max<uint64_t>(hwm, c->h_ctrl->xhwm);
-  }
-  const uint32_t xf = HOLD_XSLOT | HOLD_XGROW;
-  if (!(hold & xf)) {
-    for (sgn_ctx* c : sh)
-      if (int rc = resolve_hold(c)) return rc;
-    return 0;
-  }
-  for (sgn_ctx* c : sh) {  // the inbox flags are this function's: cleared before any growth
-    c->h_ctrl->hold &= ~xf;
-    SGN_HIP(c, hipMemcpy((char*)c->S.ctrl + offsetof(Ctrl, hold), &c->h_ctrl->hold, 4, hipMemcpyHostToDevice));
-  }
-  if (hold & HOLD_XSLOT) {
-    // each sender's runs past a peer's slot (spill-area entries tagged SPILL_PEER | peer)
-    std::vector<std::vector<std::vector<EvRec>>> out(sh.size());
-    for (size_t i = 0; i < sh.size(); i++) {
-      sgn_ctx* c = sh[i];
-      const DevSim& S = c->S;
-      out[i].assign(c->nranks, {});
-      const uint64_t n = std::min<uint64_t>(c->h_ctrl->spill_n, S.spill_cap);
-      if (!n) continue;
-      std::vector<uint32_t> idx(n);
-      std::vector<EvRec> rec(n);
-      SGN_HIP(c, hipMemcpy(idx.data(), (const void*)S.spill_idx, n * 4, hipMemcpyDeviceToHost));
-      SGN_HIP(c, hipMemcpy(rec.data(), (const void*)S.spill, n * sizeof(EvRec), hipMemcpyDeviceToHost));
-      bool any = false;
-      for (uint64_t k = 0; k < n; k++)
-        if ((idx[k] & SPILL_PEER) && idx[k] != SPILL_DEAD) {
-          out[i][idx[k] & ~SPILL_PEER].push_back(rec[k]);
-          idx[k] = SPILL_DEAD;
-          any = true;
-        }
-      if (any) SGN_HIP(c, hipMemcpy((void*)S.spill_idx, idx.data(), n * 4, hipMemcpyHostToDevice));
-    }
-    if (!peers) {
-      for (size_t i = 0; i < sh.size(); i++)
-        for (uint32_t q = 0; q < sh[i]->nranks; q++) {
-          sh[q]->x_moved += out[i][q].size();
-          if (int rc = inject_runs(sh[q], out[i][q])) return rc;
-        }
-    } else {
-      std::vector<EvRec> in;
-      if (int rc = comm_xmove_spills(sh[0], out[0], &in)) return rc;
-      sh[0]->x_moved += in.size();
-      if (int rc = inject_runs(sh[0], in)) return rc;
-    }
-    for (sgn_ctx* c : sh) c->x_over_rounds++;
-  }
-  // larger inboxes: 4x the largest per-peer count any round produced (every shard sees the same
-  // maximum: the same size everywhere), at least twice the slot
-  uint64_t ns = sh[0]->S.xislot;
-  do ns *= 2;
-  while (ns < 4 * hwm);
-  if (ns > (1ULL << 26)) return set_error(sh[0], SGN_EOVERFLOW, "inbox slot above 2^26 runs per sender");
-  for (sgn_ctx* c : sh)
-    if (int rc = xinbox_alloc(c, ns)) return rc;
-  if (!peers) {
-    std::vector<char*> base(sh.size());
-    for (size_t i = 0; i < sh.size(); i++) base[sh[i]->rank] = (char*)sh[i]->xin_mem;
-    for (sgn_ctx* c : sh) {
-      c->x_base = base;
-      if (int rc = xpeer_upload(c)) return rc;
-      c->x_mapped = true;
-    }
-  } else {
-    if (int rc = comm_xpeer_map(sh[0])) return rc;
-    if (!sh[0]->x_mapped) return set_error(sh[0], SGN_EDEVICE, "inbox growth: the peers' new inboxes could not be mapped");
-  }
-  for (sgn_ctx* c : sh) {
-    c->x_grows++;
-    if (int rc = upload_sim(c)) return rc;
-    if (int rc = sync_ctrl(c)) return rc;  // (the injected runs' occupancy and spills)
-    if (int rc = resolve_hold(c)) return rc;
-  }
-  return 0;
-}
+};
 }  // namespace
 
-// Rounds through k_rounds_x until max_rounds, the end, or a refused census (every shard's x_off
-// set: the caller goes on with per-round launches). sh: the shards of one launch — a local
-// group's (rank order) or this GPU's one (peers: the census and messages cross GPUs).
-int run_xpersist(const std::vector<sgn_ctx*>& sh, bool peers, uint64_t max_rounds, uint64_t* rounds_done) {
-  sgn_ctx* c0 = sh[0];
-  for (sgn_ctx* c : sh)
-    if (int rc = sync_ctrl(c)) return rc;
-  const uint64_t r_start = c0->h_ctrl->rounds;
-  uint64_t enq = 0;
-  int rc = 0;
-  // (a round still held from an earlier call: its pools first)
-  if (!rc) rc = x_resolve(sh, peers);
-  while (!rc && c0->h_ctrl->active && enq < max_rounds && !c0->paused) {
-    const uint32_t n = (uint32_t)std::min<uint64_t>(kPersistRounds, max_rounds - enq);
-    const int lr = x_launch(sh, peers, n);
-    if (lr < 0) return lr;
-    if (lr == 0) SGN_HIP(c0, hipStreamSynchronize(c0->stream));
-    for (sgn_ctx* c : sh)
-      if ((rc = sync_ctrl(c))) break;
-    if (rc) break;
-    if (lr == 1 || census_verdict(c0, (uint32_t)c0->x_epoch) != 1) {
-      // not resident (here or on a peer): nothing ran; per-round launches from now on
-      for (sgn_ctx* c : sh) {
-        c->x_off = true;
-        c->x_mode = 1;
-        c->persist_fallbacks++;
-      }
-      break;
-    }
-    rc = x_resolve(sh, peers);
-    enq = c0->h_ctrl->rounds - r_start;
-  }
-  for (sgn_ctx* c : sh)  // (the per-round path counts its sends in row 0 from zero)
-    if (c->S.xout_n) (void)hipMemsetAsync((void*)c->S.xout_n, 0, (6 * (size_t)c->nranks + 8) * 4, c->stream);
-  if (rounds_done) *rounds_done = c0->h_ctrl->rounds - r_start;
-  return rc;
+const RoundKernels& round_kernels(uint32_t tkind) {
+  static const RoundKernelTable t;
+  return t.k[tkind == SGN_TRAFFIC_TGEN ? 0 : tkind == SGN_TRAFFIC_EXTERNAL ? 1 : 2];
+}
+const void* import_kernel() { return (const void*)k_import; }
+
+void launch_k_import(hipStream_t st, const DevSim& S) {
+  hipLaunchKernelGGL(k_import, dim3(kImportBlocks), dim3(256), 0, st, S);
+}
+void launch_k_inject(hipStream_t st, const DevSim* Sp, const EvRec* recs, uint32_t n) {
+  hipLaunchKernelGGL(k_inject, dim3((n + 255) / 256), dim3(256), 0, st, Sp, recs, n);
+}
+void launch_k_relayout(hipStream_t st, const EvRec* old_pool, uint32_t old_cap, const uint64_t* old_ext, EvRec* pool,
+                       uint32_t cap, const uint64_t* ext, EvRec* ext_pool, const uint32_t* slab_n, uint32_t* cursor,
+                       uint64_t n_slabs) {
+  const uint64_t nt = n_slabs * old_cap;  // thread = (slab, position)
+  hipLaunchKernelGGL(k_relayout, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, st, old_pool, old_cap, old_ext, pool,
+                     cap, ext, ext_pool, slab_n, cursor, n_slabs);
+}
+void launch_k_relayout_ext(hipStream_t st, const uint64_t* hot, uint64_t n_hot, uint32_t max_ecap,
+                           const EvRec* old_ext_pool, const uint64_t* old_ext, uint32_t old_cap, EvRec* pool,
+                           uint32_t cap, const uint64_t* ext, EvRec* ext_pool, const uint32_t* slab_n) {
+  const uint64_t ne = n_hot * max_ecap;  // thread = (hot slab of the list, position)
+  hipLaunchKernelGGL(k_relayout_ext, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, st, hot, n_hot, max_ecap,
+                     old_ext_pool, old_ext, old_cap, pool, cap, ext, ext_pool, slab_n);
+}
+void launch_k_respill(hipStream_t st, const EvRec* spill, const uint32_t* spill_idx, uint64_t n, EvRec* pool,
+                      uint32_t cap, const uint64_t* ext, EvRec* ext_pool, uint32_t* cursor, uint32_t* lost) {
+  hipLaunchKernelGGL(k_respill, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, spill, spill_idx, n, pool, cap, ext,
+                     ext_pool, cursor, lost);
+}
+void launch_k_rng(hipStream_t st, const DevSim* Sp, const uint32_t* hosts, const uint32_t* count, const uint64_t* off,
+                  uint32_t n, uint64_t* out) {
+  hipLaunchKernelGGL(k_rng, dim3((n + 63) / 64), dim3(64), 0, st, Sp, hosts, count, off, n, out);
+}
+void launch_k_rng_set(hipStream_t st, const DevSim* Sp, const uint64_t* states, uint32_t n) {
+  hipLaunchKernelGGL(k_rng_set, dim3((n + 63) / 64), dim3(64), 0, st, Sp, states, n);
+}
+void launch_k_next_local(hipStream_t st, const DevSim* Sp, uint32_t lo, uint32_t n, uint64_t* out) {
+  hipLaunchKernelGGL(k_next_local, dim3((n + 255) / 256), dim3(256), 0, st, Sp, lo, n, out);
+}
+void launch_k_next_packet(hipStream_t st, uint32_t n_buckets, const DevSim* Sp, uint32_t lo, uint32_t n, uint32_t g0,
+                          uint32_t ng, uint64_t* out) {
+  hipLaunchKernelGGL(k_next_packet, dim3(n_buckets * ng), dim3(64), 0, st, Sp, lo, n, g0, ng, out);
+}
+void launch_k_codel_law_test(hipStream_t st, uint64_t n, uint64_t* out) {
+  hipLaunchKernelGGL(k_codel_law_test, dim3(1024), dim3(256), 0, st, n, out);
 }
 
-// A resolved round edge on every shard of sh (sgn_shards_*): what the run loops do between their
-// launches. A round k_import held for a full-slot exchange is completed first (RCCL transport; a
-// local group completes it inside sgn_run_local_group and never returns with one), then the held
-// flags: inbox overflow and growth across the shards, each shard's own pools and re-layout.
-int shards_resolve(const std::vector<sgn_ctx*>& sh, bool peers) {
-  for (sgn_ctx* c : sh) {
-    c->ctrl_fresh = false;
-    if (int rc = sync_ctrl(c)) return rc;
-    if (!c->h_ctrl->xspill) continue;
-    if (!peers)
-      return set_error(c, SGN_ESTATE, "a round's full-slot exchange is incomplete: run the group first");
-    if (int rc = comm_complete_spill(c)) return rc;
-  }
-  bool held = false;
-  for (sgn_ctx* c : sh) held = held || c->h_ctrl->hold || c->h_ctrl->spill_n;
-  if (!held) return 0;
-  if (int rc = x_resolve(sh, peers)) return rc;
-  for (sgn_ctx* c : sh)
-    if (int rc = sync_ctrl(c)) return rc;
-  return 0;
-}
-
-// The exchange layer after a shard's state went back to a snapshot (sgn_shards_snapshot_restore).
-// The inbox keeps its size and its mappings, but its message granules carry the global round
-// number as their tag and the rewound rounds repeat those numbers: a receiver would take the
-// first pass's message for the round's. The headers are zeroed (no tag matches a round, as in a
-// new inbox). Slots and bins hold no run at a launch's end; the census words carry launch epochs.
-int xlayer_rewind(sgn_ctx* ctx) {
-  const DevSim& S = ctx->S;
-  if (ctx->xin_mem) {
-    const XLay l = xlay(ctx->nranks, S.xislot, S.G, S.xbk);
-    SGN_HIP(ctx, hipMemsetAsync((char*)ctx->xin_mem + l.hdr, 0, l.cen - l.hdr, ctx->stream));
-  }
-  // (the per-round path counts its sends in row 0 from zero: run_xpersist's end)
-  if (S.xout_n) SGN_HIP(ctx, hipMemsetAsync((void*)S.xout_n, 0, (6 * (size_t)ctx->nranks + 8) * 4, ctx->stream));
-  if (ctx->gexec && ctx->gsz != ctx->xsz_cur) drop_graph(ctx);
-  return 0;
-}
-
-void free_sim(sgn_ctx* ctx) {
-  drop_graph(ctx);
-  xinbox_release(ctx);
-  if (ctx->x_hxl) (void)hipHostFree(ctx->x_hxl);
-  ctx->x_hxl = nullptr;
-  ctx->d_xp = ctx->d_xl = nullptr;  // (in allocs)
-  ctx->x_mapped = false;
-  ctx->rng_held.clear();
-  if (ctx->d_rng_stage) hipFree(ctx->d_rng_stage);
-  ctx->d_rng_stage = nullptr;
-  ctx->rng_stage_cap = 0;
-  for (void* p : ctx->allocs) hipFree(p);
-  ctx->allocs.clear();
-  ctx->sim_bytes = 0;
-  if (ctx->d_stage) hipFree(ctx->d_stage);
-  ctx->d_stage = nullptr;
-  ctx->stage_cap = 0;
-  if (ctx->h_ctrl) {
-    hipHostFree(ctx->h_ctrl);
-    ctx->h_ctrl = nullptr;
-  }
-  if (ctx->h_mirror) {
-    hipHostFree(ctx->h_mirror);
-    ctx->h_mirror = nullptr;
-  }
-  ctx->ctrl_fresh = false;
-  ctx->sim_ready = false;
-}
+uint64_t layout_sig_engine() { return kLayoutSig; }
 
 }  // namespace sgn
-
-extern "C" {
-
-int sgn_trace_enable(sgn_ctx* ctx, uint64_t capacity) {
-  if (!ctx) return SGN_EINVAL;
-  if (ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "sgn_trace_enable must precede sgn_sim_init");
-  ctx->trace_cap = capacity;
-  return 0;
-}
-
-int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  if (!ctx || !cfg || !tr) return SGN_EINVAL;
-  if (!ctx->routes_ready) return set_error(ctx, SGN_ESTATE, "sgn_routes_build must precede sgn_sim_init");
-  if (!ctx->hosts_ready) return set_error(ctx, SGN_ESTATE, "sgn_hosts_set must precede sgn_sim_init");
-  if (tr->kind != SGN_TRAFFIC_PERIODIC && tr->kind != SGN_TRAFFIC_TGEN &&
-      tr->kind != SGN_TRAFFIC_EXTERNAL)
-    return set_error(ctx, SGN_EINVAL, "unknown traffic kind");
-  if (cfg->out_fifo_cap == 0 || cfg->codel_cap == 0)
-    return set_error(ctx, SGN_EINVAL, "out_fifo_cap and codel_cap must be >= 1");
-  if (tr->kind == SGN_TRAFFIC_PERIODIC && tr->payload_len > 0xFFFFu)
-    return set_error(ctx, SGN_EINVAL, "payload_len must fit a UDP datagram");
-  if (tr->kind == SGN_TRAFFIC_TGEN && (tr->n_servers == 0 || !tr->server_hosts))
-    return set_error(ctx, SGN_EINVAL, "TGEN traffic needs servers");
-  if (tr->kind == SGN_TRAFFIC_TGEN && tr->req_payload > 0xFFFFu)
-    return set_error(ctx, SGN_EINVAL, "req_payload must fit a UDP datagram");
-  if (ctx->sim_ready) free_sim(ctx);
-  SGN_HIP(ctx, hipSetDevice(ctx->device));
-
-  DevSim S{};
-  const uint32_t nH = ctx->hi - ctx->lo;
-  const uint32_t N = ctx->n_all;
-  ctx->persist_off = false;
-  ctx->res_epoch = ctx->res_base = 0;  // (the new control block's census words are zero)
-  ctx->codel_grows = ctx->cal_grows = ctx->cal_spill_runs = ctx->xslot_grows = ctx->rounds_held = 0;
-  ctx->codel_allocs_before = 0;
-  ctx->ext_slabs = ctx->spill_grows = 0;
-  ctx->h_ext.clear();
-  ctx->failed.clear();
-  S.n_all = N;
-  S.lo = ctx->lo;
-  S.nH = nH;
-  S.U = ctx->U;
-  S.end_time = SIM_START + cfg->stop_time_ns;
-  S.boot_end = SIM_START + cfg->bootstrap_end_ns;
-  S.runahead_cfg = cfg->runahead_ns;
-  S.dynamic = cfg->use_dynamic_runahead ? 1 : 0;
-  S.fifo_cap = cfg->out_fifo_cap;
-  if (cfg->interface_qdisc > SGN_QDISC_ROUND_ROBIN) return set_error(ctx, SGN_EINVAL, "unknown interface_qdisc");
-  S.qdisc_rr = cfg->interface_qdisc == SGN_QDISC_ROUND_ROBIN ? 1u : 0u;
-  // CoDel page pool: codel_cap run slots per host on average, at least one page per host
-  // (its first) plus 64 to share
-  {
-    const uint64_t pages = std::max<uint64_t>((uint64_t)nH + 64, ((uint64_t)nH * cfg->codel_cap + CQ_PAGE - 1) / CQ_PAGE);
-    if (pages >= (1ULL << 28)) return set_error(ctx, SGN_EINVAL, "codel_cap: CoDel page pool above 2^28 pages");
-    S.cq_pages = (uint32_t)pages;
-    S.div_cq.init(pages);
-  }
-  S.trace_on = ctx->trace_cap > 0;
-  S.tkind = tr->kind;
-  S.payload_len = tr->payload_len;
-  S.unknown_permille = tr->unknown_dst_permille;
-  S.req_payload = tr->req_payload;
-  S.n_servers = tr->kind == SGN_TRAFFIC_TGEN ? tr->n_servers : 0;
-  S.flow_seed = tr->flow_seed;
-  S.period = tr->period_ns;
-  S.period_jitter = tr->period_jitter_ns;
-  for (int i = 0; i < 3; i++) S.file_bytes[i] = tr->file_bytes[i];
-
-  const uint64_t min_possible = ctx->lat_min, max_lat = ctx->lat_max;
-  S.min_possible = min_possible;
-  S.max_lat = max_lat;
-  if (min_possible == 0) return set_error(ctx, SGN_EINVAL, "route latency 0 (Runahead::new asserts)");
-
-  // routing (device copies made by sgn_routes_build)
-  S.rlat = (decltype(S.rlat))ctx->d_lat;
-  S.rloss = (decltype(S.rloss))ctx->d_loss;
-  uint32_t* d_unode = dalloc<uint32_t>(ctx, N);
-  uint32_t* d_ip = dalloc<uint32_t>(ctx, N);
-  uint32_t* d_dk = dalloc<uint32_t>(ctx, ctx->dns_key.size());
-  uint32_t* d_dv = dalloc<uint32_t>(ctx, ctx->dns_val.size());
-  if (!d_unode || !d_ip || !d_dk || !d_dv) return set_error(ctx, SGN_ENOMEM, "device allocation failed");
-  SGN_HIP(ctx, hipMemcpy(d_unode, ctx->unode.data(), N * 4, hipMemcpyHostToDevice));
-  SGN_HIP(ctx, hipMemcpy(d_ip, ctx->ip.data(), N * 4, hipMemcpyHostToDevice));
-  SGN_HIP(ctx, hipMemcpy(d_dk, ctx->dns_key.data(), ctx->dns_key.size() * 4, hipMemcpyHostToDevice));
-  SGN_HIP(ctx, hipMemcpy(d_dv, ctx->dns_val.data(), ctx->dns_val.size() * 4, hipMemcpyHostToDevice));
-  S.unode = (decltype(S.unode))d_unode;
-  S.ip = (decltype(S.ip))d_ip;
-  S.dns_key = (decltype(S.dns_key))d_dk;
-  S.dns_val = (decltype(S.dns_val))d_dv;
-  S.dns_mask = ctx->dns_mask;
-  std::vector<uint8_t> is_server(N, 0);
-  if (tr->kind == SGN_TRAFFIC_TGEN) {
-    uint32_t* d_sv = dalloc<uint32_t>(ctx, tr->n_servers);
-    if (!d_sv) return set_error(ctx, SGN_ENOMEM, "device allocation failed");
-    for (uint32_t i = 0; i < tr->n_servers; i++) {
-      if (tr->server_hosts[i] >= N) return set_error(ctx, SGN_EINVAL, "server host out of range");
-      is_server[tr->server_hosts[i]] = 1;
-    }
-    SGN_HIP(ctx, hipMemcpy(d_sv, tr->server_hosts, tr->n_servers * 4, hipMemcpyHostToDevice));
-    S.servers = (decltype(S.servers))d_sv;
-  }
-
-  // ---- host slots: every shard's HostId range, permuted so that hosts of one kind share
-  // waves (TGEN: servers by uplink, then clients by downlink; otherwise by bandwidth, then by
-  // graph node: a wave's sends then read one row of the route table, and an XCD's workgroups
-  // a few hundred rows instead of all of them — config D's ~1 k hosts per node fill whole
-  // waves, so its random-peer route lookups become L2 hits). The
-  // permutation only places hosts on lanes; semantics follow HostIds. SGN_HOST_ORDER=id keeps
-  // HostId order (test hook). Every shard computes every shard's permutation (same inputs).
-  {
-    const bool by_id = getenv("SGN_HOST_ORDER") && std::string(getenv("SGN_HOST_ORDER")) == "id";
-    ctx->sid_of.assign(N, 0);
-    std::vector<uint32_t> order;
-    for (uint32_t rk = 0; rk < ctx->nranks; rk++) {
-      uint32_t lo = 0, hi = 0;
-      sgn_shard_range(N, rk, ctx->nranks, &lo, &hi);
-      order.resize(hi - lo);
-      for (uint32_t i = lo; i < hi; i++) order[i - lo] = i;
-      if (!by_id) {
-        auto key = [&](uint32_t i) {
-          if (tr->kind == SGN_TRAFFIC_TGEN)
-            return std::make_tuple(is_server[i] ? 0u : 1u, is_server[i] ? ctx->bw_up[i] : ctx->bw_down[i], (uint64_t)i);
-          return std::make_tuple(0u, ctx->bw_up[i] ^ (ctx->bw_down[i] << 1), (uint64_t)ctx->unode[i] << 32 | i);
-        };
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
-      }
-      for (uint32_t k = 0; k < hi - lo; k++) ctx->sid_of[order[k]] = lo + k;
-      if (rk == ctx->rank) ctx->host_of = order;
-    }
-  }
-  // ---- per-host state records (one per slot), initialised on the host ----
-  std::vector<HostRec> recs(nH);
-  std::vector<HostConst> hk(nH);
-  std::vector<uint64_t> nextloc(nH, INVALID);
-  std::memset(recs.data(), 0, recs.size() * sizeof(HostRec));
-  std::memset(hk.data(), 0, hk.size() * sizeof(HostConst));
-  for (uint32_t h = 0; h < nH; h++) {
-    const uint32_t g = ctx->host_of[h];
-    HostRec& r = recs[h];
-    HostConst& k = hk[h];
-    k.gid = r.k_gid = g;
-    k.ip = r.k_ip = ctx->ip[g];
-    k.unode = r.k_unode = ctx->unode[g];
-    // Xoshiro256PlusPlus::seed_from_u64 (SplitMix64 fill), host.rs:234
-    uint64_t sm = ctx->seed[g];
-    for (int i = 0; i < 4; i++) r.rng[i] = host_splitmix(sm);
-    r.st0 = r.st1 = r.st2 = INVALID;
-    // create_token_bucket (relay/mod.rs:278-288) for inet_out (up) and inet_in (down)
-    for (int w = 0; w < 2; w++) {
-      const uint64_t bps = (w == 0 ? ctx->bw_up[g] : ctx->bw_down[g]) / 8;
-      const uint64_t inc = std::max<uint64_t>(1, bps / 1000);
-      k.tb_inc[w] = r.k_tbinc[w] = inc;  // (capacity = inc + MTU, the bucket starts full)
-      r.tb_bal[w] = inc + SGN_CONFIG_MTU;
-      r.tb_last[w] = SIM_START;
-    }
-    for (int i = 0; i < 3; i++) r.dig[i] = SGN_DIGEST_SEED;
-    r.rc_dst = NO_HOST;  // empty route cache
-    r.cq_head = h * CQ_PAGE;  // CoDel chain: page h
-    r.cq_tp = h;
-    if (is_server[g]) r.flags |= F_SERVER;
-    const bool has_app = tr->kind == SGN_TRAFFIC_PERIODIC || (tr->kind == SGN_TRAFFIC_TGEN && !is_server[g]);
-    if (has_app) {
-      r.flags |= F_HAS_APP;
-      const uint64_t t = SIM_START + sgn_app_start_rel(tr->flow_seed, g, tr->start_ns, tr->start_jitter_ns);
-      const uint64_t e = r.eid++;
-      if (t < S.end_time) {
-        r.st2 = t;
-        r.se2 = e;
-        nextloc[h] = t;
-      }
-    }
-  }
-  auto up64 = [&](const std::vector<uint64_t>& v, auto* out) -> int {
-    *out = (std::remove_reference_t<decltype(*out)>)dalloc<uint64_t>(ctx, v.size());
-    if (!*out) return set_error(ctx, SGN_ENOMEM, "device allocation failed");
-    SGN_HIP(ctx, hipMemcpy((void*)*out, v.data(), v.size() * 8, hipMemcpyHostToDevice));
-    return 0;
-  };
-  auto up32 = [&](const std::vector<uint32_t>& v, auto* out) -> int {
-    *out = (std::remove_reference_t<decltype(*out)>)dalloc<uint32_t>(ctx, v.size());
-    if (!*out) return set_error(ctx, SGN_ENOMEM, "device allocation failed");
-    SGN_HIP(ctx, hipMemcpy((void*)*out, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    return 0;
-  };
-  int rc = 0;
-  if ((rc = up32(ctx->sid_of, &S.sid_of)) || (rc = up32(ctx->host_of, &S.host_of))) return rc;
-  {  // the packet path's peer and route forms (send_batch: two loads per route-cache miss)
-    std::vector<uint64_t> pe(N);
-    for (uint32_t i = 0; i < N; i++) pe[i] = (uint64_t)ctx->sid_of[i] | ((uint64_t)ctx->unode[i] << 32);
-    if ((rc = up64(pe, &S.peer))) return rc;
-    // the 4-byte form when slot ids and node indices fit together (sid < N, node < U)
-    uint32_t sb = 1, ub = 1;
-    while (sb < 32 && (1ull << sb) < N) sb++;
-    while (ub < 32 && (1ull << ub) < ctx->U) ub++;
-    S.peer32 = nullptr;
-    S.peer_sb = sb;
-    if (sb + ub <= 32 && !getenv("SGN_PEER64")) {
-      std::vector<uint32_t> p32(N);
-      for (uint32_t i = 0; i < N; i++) p32[i] = ctx->sid_of[i] | (ctx->unode[i] << sb);
-      if ((rc = up32(p32, &S.peer32))) return rc;
-    }
-    if ((rc = ensure_host_routes(ctx))) return rc;
-    const size_t UU = (size_t)ctx->U * ctx->U;
-    std::vector<RouteEnt> re(UU);
-    for (size_t i = 0; i < UU; i++) {
-      // reliability = (f64)(1.0f - loss) (worker.rs:363-371), exactly as the device would
-      volatile float rel32 = 1.0f - ctx->h_loss[i];
-      re[i].lat = ctx->h_lat[i];
-      re[i].T = (uint64_t)((double)rel32 * 9007199254740992.0);
-    }
-    RouteEnt* d = (RouteEnt*)dev_alloc(ctx, UU * sizeof(RouteEnt), false);
-    if (!d) return set_error(ctx, SGN_ENOMEM, "device allocation failed (route table)");
-    SGN_HIP(ctx, hipMemcpy(d, re.data(), UU * sizeof(RouteEnt), hipMemcpyHostToDevice));
-    S.route = (decltype(S.route))d;
-  }
-  S.hrec = (decltype(S.hrec))dalloc<HostRec>(ctx, nH);
-  S.codel = (decltype(S.codel))dalloc<CodelEnt>(ctx, (size_t)S.cq_pages * CQ_PAGE);
-  S.cq_next = (decltype(S.cq_next))dalloc<uint32_t>(ctx, S.cq_pages);
-  {  // host slot h starts with page h; pages nH.. are the free ring's first entries
-    std::vector<uint32_t> fr(S.cq_pages, 0);
-    for (uint32_t i = 0; i + nH < S.cq_pages; i++) fr[i] = nH + i;
-    if ((rc = up32(fr, &S.cq_free))) return rc;
-  }
-  S.rb_free = (decltype(S.rb_free))dalloc<uint64_t>(ctx, 3);
-  S.fifo = (decltype(S.fifo))dalloc<FifoEnt>(ctx, (size_t)nH * cfg->out_fifo_cap);
-  S.fifo_addr = nullptr;
-  if (ctx->trace_cap) {
-    S.fifo_addr = (decltype(S.fifo_addr))dalloc<uint32_t>(ctx, (size_t)nH * cfg->out_fifo_cap);
-    if (!S.fifo_addr) return set_error(ctx, SGN_ENOMEM, "device allocation failed (trace)");
-  }
-  if (!S.hrec || !S.codel || !S.fifo || !S.cq_next || !S.rb_free)
-    return set_error(ctx, SGN_ENOMEM, "device allocation failed (host state)");
-  SGN_HIP(ctx, hipMemcpy((void*)S.hrec, recs.data(), recs.size() * sizeof(HostRec), hipMemcpyHostToDevice));
-  S.htile = nullptr;
-  if (tr->kind == SGN_TRAFFIC_PERIODIC) {  // the hot lines, tiled (kSoa)
-    const size_t nt = ((size_t)nH + 63) / 64;
-    std::vector<uint64_t> tile(nt * 8 * 64 * 2, 0);
-    for (uint32_t h = 0; h < nH; h++)
-      for (uint32_t c = 0; c < 8; c++) std::memcpy(&tile[2 * hot_idx(h, c)], (const char*)&recs[h] + 16 * c, 16);
-    S.htile = (decltype(S.htile))dalloc<uint64_t>(ctx, tile.size());
-    if (!S.htile) return set_error(ctx, SGN_ENOMEM, "device allocation failed (host tiles)");
-    SGN_HIP(ctx, hipMemcpy((void*)S.htile, tile.data(), tile.size() * 8, hipMemcpyHostToDevice));
-  }
-  {
-    HostConst* dk = dalloc<HostConst>(ctx, nH);
-    S.n_cnt = (decltype(S.n_cnt))dalloc<uint64_t>(ctx, (size_t)N_CNT * nH);
-    S.maxq = (decltype(S.maxq))dalloc<uint32_t>(ctx, nH);
-    if (!dk || !S.n_cnt || !S.maxq) return set_error(ctx, SGN_ENOMEM, "device allocation failed (host state)");
-    SGN_HIP(ctx, hipMemcpy(dk, hk.data(), hk.size() * sizeof(HostConst), hipMemcpyHostToDevice));
-    S.hconst = (decltype(S.hconst))dk;
-  }
-  if ((rc = up64(nextloc, &S.nextloc))) return rc;
-  S.npeer = nullptr;
-  if (tr->kind == SGN_TRAFFIC_PERIODIC) {  // every app counter starts at 0
-    std::vector<uint32_t> np(nH);
-    for (uint32_t h = 0; h < nH; h++) {
-      uint32_t peer = NO_HOST, uip = 0;
-      np[h] = sgn_periodic_dst(tr->flow_seed, ctx->host_of[h], 0, N, tr->unknown_dst_permille, &peer, &uip) ? peer : NO_HOST;
-    }
-    if ((rc = up32(np, &S.npeer))) return rc;
-  }
-
-  // ---- calendar: bucket width >= any window length, horizon > max latency ----
-  // The shortest possible window (Runahead::get, runahead.rs:44-57): a window spans at least
-  // one bucket, and in dynamic mode possibly many (executed bucket by bucket).
-  uint64_t BW = std::max<uint64_t>(1, std::max(min_possible, cfg->runahead_ns));
-  // Every pending event lies in [ws, we + max_lat): sends happen before the window end and
-  // arrive at most max_lat later (worker.rs:386-390). A static window is BW long; a dynamic
-  // one is max(min used latency, configured runahead) (runahead.rs:44-57), i.e. up to
-  // max(max_lat, runahead). The calendar spans that plus one partial bucket at each end;
-  // send_batch checks the horizon on the device (OVF_HORIZON), so a violation is reported.
-  // The persistent kernel resets a round's consumed buckets during the next round, so one more
-  // window of slack keeps the next round's sends off them (see k_rounds).
-  const uint64_t wmax = cfg->use_dynamic_runahead ? std::max<uint64_t>(BW, std::max(max_lat, cfg->runahead_ns)) : BW;
-  uint64_t NB = (3 * wmax + max_lat) / BW + 8;
-  if (NB > (1u << 20)) return set_error(ctx, SGN_EINVAL, "calendar would need > 2^20 buckets");
-  while (NB & (NB - 1)) NB += NB & (~NB + 1);  // round up to a power of two
-  // hosts per k_execute wave: fewer than 64 spreads the (divergent, per-lane serial) host
-  // work of a round over more waves; sgn_sim_config.hosts_per_wave (0 = default 64)
-  uint32_t gsz = cfg->hosts_per_wave ? cfg->hosts_per_wave : 64;
-  if (const char* e = getenv("SGN_HOSTS_PER_WAVE")) gsz = (uint32_t)atoi(e);
-  if (gsz == 0 || gsz > GROUP_MAX || (gsz & (gsz - 1)))
-    return set_error(ctx, SGN_EINVAL, "hosts_per_wave must be a power of two in [1, 64]");
-  S.gsh = (uint32_t)__builtin_ctz(gsz);
-  const uint64_t G = (nH + gsz - 1) / gsz;
-  uint64_t cap = cfg->event_capacity ? cfg->event_capacity : (1ULL << 22);
-  uint64_t CAP = cap / ((NB + 1) * G);
-  CAP = std::max<uint64_t>(CAP_MIN, std::min<uint64_t>(CAP_MAX, CAP));
-  // test hook: small slabs, so that rounds spill runs and the calendar is re-laid out
-  if (const char* e = getenv("SGN_SLAB_CAP")) CAP = std::max<uint64_t>(16, std::min<uint64_t>(CAP_MAX, atoll(e)));
-  S.NB = (uint32_t)NB;
-  S.G = (uint32_t)G;
-  S.CAP = (uint32_t)CAP;
-  S.BW = BW;
-  S.bw_div.init(BW);
-  S.div_n.init(std::max<uint64_t>(1, N));
-  S.div_1000.init(1000);
-  S.div_ns.init(std::max<uint64_t>(1, S.n_servers));
-  S.pool = (decltype(S.pool))dalloc<EvRec>(ctx, (NB + 1) * G * CAP);
-  S.w_cnt = (decltype(S.w_cnt))dalloc<uint64_t>(ctx, W_N * G);
-  if (!S.w_cnt) return set_error(ctx, SGN_ENOMEM, "device allocation failed (wave slots)");
-  S.slab_n = (decltype(S.slab_n))dalloc<uint32_t>(ctx, (NB + 1) * G);
-  if (!S.pool || !S.slab_n) return set_error(ctx, SGN_ENOMEM, "device allocation failed (event calendar)");
-  std::vector<uint32_t> bslab(NB);
-  for (uint64_t b = 0; b < NB; b++) bslab[b] = (uint32_t)b;
-  if ((rc = up32(bslab, &S.bucket_slab))) return rc;
-  std::vector<uint64_t> bmin(NB, INVALID);
-  if ((rc = up64(bmin, &S.bucket_min))) return rc;
-  // SGN_STAMPS=1: per-group stamps; =2: also the persistent kernel's per-round timeline (one
-  // atomic min and max per workgroup and round on shared words: it slows the rounds it times)
-  if (const char* e = getenv("SGN_STAMPS")) {
-    S.stamps = (decltype(S.stamps))dalloc<uint64_t>(ctx, SGN_STAMP_WORDS * G);
-    if (atoi(e) >= 2) {
-      S.rdbg_wg = atoi(e) >= 3 ? 1u : 0u;
-      S.rdbg = (decltype(S.rdbg))dalloc<uint64_t>(ctx, S.rdbg_wg ? (size_t)8 * 128 * 2048 : 8 * 128);
-    }
-  }
-  if (ctx->trace_cap) {
-    S.trace = (decltype(S.trace))dalloc<sgn_trace_rec>(ctx, ctx->trace_cap);
-    if (!S.trace) return set_error(ctx, SGN_ENOMEM, "device allocation failed (trace)");
-    S.trace_cap = ctx->trace_cap;
-  }
-  ctx->handles.clear();
-  ctx->drain_held.clear();
-  ctx->submit_seq.assign(nH, 0u);
-  if (tr->kind == SGN_TRAFFIC_EXTERNAL) {
-    const uint64_t dc = ctx->drain_cap ? ctx->drain_cap : (1ULL << 20);
-    S.drain = (decltype(S.drain))dalloc<sgn_drain_rec>(ctx, dc);
-    if (!S.drain) return set_error(ctx, SGN_ENOMEM, "device allocation failed (drain buffer)");
-    S.drain_cap = dc;
-  }
-  // multi-GPU exchange slots
-  S.n_ranks = ctx->nranks;
-  S.rank = ctx->rank;
-  {
-    std::vector<uint32_t> rl(ctx->nranks + 1);
-    for (uint32_t r = 0; r <= ctx->nranks; r++) {
-      uint32_t lo = 0, hi = 0;
-      sgn_shard_range(N, r < ctx->nranks ? r : ctx->nranks - 1, ctx->nranks, &lo, &hi);
-      rl[r] = r < ctx->nranks ? lo : N;
-    }
-    if ((rc = up32(rl, &S.rank_lo))) return rc;
-  }
-  if (ctx->nranks > 1) {
-    if (!ctx->comm && !ctx->comm_local)
-      return set_error(ctx, SGN_ESTATE, "multi-shard context needs sgn_comm_init (or sgn_comm_init_local) before sgn_sim_init");
-    S.xslot = (uint32_t)ctx->xslot;
-    // per peer a block of 1 + xslot records: the 32-byte round-edge message, then the runs
-    S.xout = (decltype(S.xout))dalloc<EvRec>(ctx, (size_t)ctx->nranks * (ctx->xslot + XHDR));
-    S.xin = (decltype(S.xin))dalloc<EvRec>(ctx, (size_t)ctx->nranks * (ctx->xslot + XHDR));
-    // (per-round launches count in row 0; k_rounds_x in row round % 3)
-    // (k_rounds_x: rows [3][n_ranks] of slot counts, then [3][n_ranks] of totals, bins included)
-    S.xout_n = (decltype(S.xout_n))dalloc<uint32_t>(ctx, ctx->nranks * 6 + 8);
-    S.xin_n = (decltype(S.xin_n))dalloc<uint32_t>(ctx, ctx->nranks * 2 + 8);
-    if (!S.xout || !S.xin || !S.xout_n || !S.xin_n) return set_error(ctx, SGN_ENOMEM, "device allocation failed (exchange)");
-    // persistent rounds: the second barrier's counters, the XPeer table, the launch descriptor
-    // and this shard's inbox (SGN_XISLOT: a smaller first slot, a test hook for the growth path)
-    S.rb2_cnt = (decltype(S.rb2_cnt))dalloc<uint32_t>(ctx, 3 * RB_CB_MAX);
-    ctx->d_xp = dalloc<XPeer>(ctx, ctx->nranks);
-    ctx->d_xl = dalloc<XLaunch>(ctx, 1);
-    if (!S.rb2_cnt || !ctx->d_xp || !ctx->d_xl) return set_error(ctx, SGN_ENOMEM, "device allocation failed (exchange)");
-    S.xp = (decltype(S.xp))ctx->d_xp;
-    S.xown = kOwnFile;
-    if (const char* e = getenv("SGN_XOWN")) S.xown = (uint32_t)atoi(e);
-    // inbox bins: xbk runs per (parity, sender, receiving group), a power of two;
-    // SGN_XBIN: another size, 0 = none (every import through the slots)
-    ctx->x_G.assign(ctx->nranks, 0u);
-    S.xgx = 0;
-    for (uint32_t q = 0; q < ctx->nranks; q++) {
-      uint32_t lo = 0, hi = 0;
-      sgn_shard_range(N, q, ctx->nranks, &lo, &hi);
-      ctx->x_G[q] = (hi - lo + gsz - 1) / gsz;
-      S.xgx = std::max(S.xgx, ctx->x_G[q]);
-    }
-    S.xbk = kXBin;
-    if (const char* e = getenv("SGN_XBIN")) {  // (a test hook: small bins send runs to the slots)
-      const uint32_t v = (uint32_t)atoi(e);
-      S.xbk = 0;
-      if (v) {
-        S.xbk = 1;
-        while (S.xbk < v && S.xbk < (1u << 12)) S.xbk *= 2;
-      }
-    }
-    S.xbin_n = nullptr;
-    if (S.xbk) {
-      S.xbin_n = (decltype(S.xbin_n))dalloc<uint32_t>(ctx, (size_t)2 * ctx->nranks * S.xgx);
-      if (!S.xbin_n) return set_error(ctx, SGN_ENOMEM, "device allocation failed (inbox bin counters)");
-    }
-    uint64_t xis = ctx->xslot;
-    if (const char* e = getenv("SGN_XISLOT")) xis = std::max<uint64_t>(1, std::min<uint64_t>(xis, (uint64_t)atoll(e)));
-    ctx->S = S;  // (xinbox_alloc / xpeer_upload work on ctx->S)
-    if ((rc = xinbox_alloc(ctx, xis)) || (rc = xpeer_upload(ctx))) return rc;
-    S = ctx->S;
-    ctx->x_off = false;
-    ctx->x_mode = 1;
-    ctx->x_epoch = ctx->x_grows = ctx->x_over_rounds = ctx->x_moved = ctx->x_launches = 0;
-    for (sgn_ctx* g : ctx->group)  // (a local group maps every member's inbox at its next run)
-      if (g) g->x_mapped = false;
-  }
-  Ctrl c{};
-  c.ws = SIM_START;  // initial window (manager.rs:506-509)
-  c.we = SIM_START + 1;
-  c.active = 1;
-  c.round_min = INVALID;
-  c.min_used = INVALID;
-  c.keep_slab = (uint32_t)NB;
-  c.keep_min = INVALID;
-  c.last_min_next = INVALID;
-  c.prev_we = SIM_START;
-  c.pause_at = EMU_MAX;
-  c.pg_tail = c.pg_avail = S.cq_pages - nH;  // the free ring holds the pages beyond the hosts' first
-  // multi-shard exchange size: RCCL rounds start at min(slot, kXszInit) runs per peer and
-  // grow with the high-water mark; a local shard group copies counts, so it uses the slot
-  ctx->xsz_cur = ctx->nranks > 1 ? (ctx->comm_local ? (uint32_t)ctx->xslot
-                                                    : (uint32_t)std::min<uint64_t>(ctx->xslot, kXszInit))
-                                 : 0;
-  // test hook: a small first size makes the first rounds hold and complete (spill path)
-  if (const char* e = getenv("SGN_XSZ_INIT"))
-    if (ctx->nranks > 1 && !ctx->comm_local)
-      ctx->xsz_cur = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(ctx->xslot, (uint64_t)atoll(e)));
-  ctx->x_spills = ctx->x_bytes = 0;
-  c.xsz = ctx->xsz_cur;
-  S.ctrl = (decltype(S.ctrl))dalloc<Ctrl>(ctx, 1);
-  if (!S.ctrl) return set_error(ctx, SGN_ENOMEM, "device allocation failed");
-  SGN_HIP(ctx, hipMemcpy(S.ctrl, &c, sizeof(c), hipMemcpyHostToDevice));
-  if (!ctx->h_ctrl) SGN_HIP(ctx, hipHostMalloc((void**)&ctx->h_ctrl, sizeof(Ctrl), 0));
-  static_assert(sizeof(Ctrl) % 8 == 0, "the control block's copy is written in u64 words");
-  if (!ctx->h_mirror) SGN_HIP(ctx, hipHostMalloc((void**)&ctx->h_mirror, kMirrorWords * 8, 0));
-  std::memset(ctx->h_mirror, 0, kMirrorWords * 8);
-  {
-    void* dm = nullptr;
-    SGN_HIP(ctx, hipHostGetDevicePointer(&dm, ctx->h_mirror, 0));
-    S.ctrl_mirror = (decltype(S.ctrl_mirror))dm;
-  }
-  *ctx->h_ctrl = c;
-  S.fuse_finalize = ctx->nranks == 1 ? 1u : 0u;
-  // PERIODIC traffic: each host receives ~BW / period runs per bucket, so a group's slab holds
-  // ~gsz * BW / period; when that is a full wave (config D: 64 hosts, one send per window) all
-  // 64 lanes load speculatively and the second round trip goes (same-box A/B: D +1.3 %, while
-  // B's ~2-run slabs measured 1 % slower at 64 and unchanged at 4 and 8)
-  // (round 4: from 4 up, twice the expected fill: config B's ~2-run slabs of 16 hosts read 4
-  // records instead of 16 — its PMC traffic was 3.4x the algorithmic bytes, mostly these
-  // speculative heads, while B's time measured the same at 4, 8 and 16 in round 3)
-  S.gspec = GATHER_SPEC;
-  if (S.tkind == SGN_TRAFFIC_PERIODIC && S.period) {
-    const uint64_t fill = ((uint64_t)gsz * BW + S.period - 1) / S.period;
-    S.gspec = 4;
-    while (S.gspec < 64 && S.gspec < 2 * fill) S.gspec *= 2;
-  }
-  if (const char* e = getenv("SGN_GATHER_SPEC")) S.gspec = std::min<uint32_t>(64, (uint32_t)atoi(e));
-  S.gspec = (uint32_t)std::min<uint64_t>(S.gspec, S.CAP);  // speculative loads stay inside the slab
-  size_round_kernels(ctx, S);
-  // persistent-round buffers (three, by round % 3): chunk minima + keep minima, counters
-  S.rb_min = (decltype(S.rb_min))dalloc<uint64_t>(ctx, 3 * RB_CH * RB_MS_MAX + 4);
-  S.rb_keep = S.rb_min + 3 * RB_CH * RB_MS_MAX;
-  S.rb_cnt = (decltype(S.rb_cnt))dalloc<uint32_t>(ctx, 3 * RB_CB_MAX + 1);
-  S.rb_occ = (decltype(S.rb_occ))dalloc<uint64_t>(ctx, 3 * RB_CH * RB_OS_MAX + 6);
-  if (!S.rb_min || !S.rb_cnt || !S.rb_occ) return set_error(ctx, SGN_ENOMEM, "device allocation failed");
-  S.fin_cnt = (decltype(S.fin_cnt))dalloc<uint32_t>(ctx, (G + 63) / 64 + 1);
-  S.fin_occ = (decltype(S.fin_occ))dalloc<uint64_t>(ctx, (G + 63) / 64);
-  if (!S.fin_occ) return set_error(ctx, SGN_ENOMEM, "device allocation failed");
-  // the calendar's spill area: runs whose slab is full until the next re-layout (a round edge
-  // holds right after a spill); sized for an eighth of the slabs, at least 2^16 runs
-  S.spill_cap = std::max<uint64_t>(1u << 16, std::min<uint64_t>(1u << 24, (NB + 1) * G * CAP / 8));
-  S.spill = (decltype(S.spill))dev_alloc(ctx, S.spill_cap * sizeof(EvRec), false);
-  S.spill_idx = (decltype(S.spill_idx))dev_alloc(ctx, S.spill_cap * 4, false);
-  if (!S.spill || !S.spill_idx) return set_error(ctx, SGN_ENOMEM, "device allocation failed (spill area)");
-  {
-    std::vector<uint64_t> inv((G + 63) / 64, INVALID);
-    if ((rc = up64(inv, &S.fin_keep)) || (rc = up64(inv, &S.fin_next))) return rc;
-  }
-  if (!S.fin_cnt) return set_error(ctx, SGN_ENOMEM, "device allocation failed");
-  ctx->d_S = dalloc<DevSim>(ctx, 1);
-  if (!ctx->d_S) return set_error(ctx, SGN_ENOMEM, "device allocation failed");
-  SGN_HIP(ctx, hipMemcpy(ctx->d_S, &S, sizeof(S), hipMemcpyHostToDevice));
-  SGN_HIP(ctx, hipDeviceSynchronize());
-  ctx->S = S;
-  ctx->sim_ready = true;
-  ctx->sim_gen++;  // (snapshots of the simulation before this one are refused from here)
-  ctx->paused = false;
-  ctx->rounds_enqueued = 0;
-  for (int i = 0; i < K_NUM; i++) ctx->kt[i] = {kKernelNames[i], 0, 0.0, 0};
-  return 0;
-}
-
-int sgn_window(sgn_ctx* ctx, uint64_t* start, uint64_t* end, int32_t* active) {
-  if (!ctx || !ctx->sim_ready) return ctx ? set_error(ctx, SGN_ESTATE, "no simulation") : SGN_EINVAL;
-  int rc = sync_ctrl(ctx);
-  if (start) *start = ctx->h_ctrl->ws;
-  if (end) *end = ctx->h_ctrl->we;
-  if (active) *active = (int32_t)ctx->h_ctrl->active;
-  return rc;
-}
-
-int sgn_round(sgn_ctx* ctx, uint64_t* min_next) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  if (!ctx || !ctx->sim_ready) return ctx ? set_error(ctx, SGN_ESTATE, "no simulation") : SGN_EINVAL;
-  if (int e = rng_release(ctx)) return e;
-  if (ctx->comm_local)
-    return set_error(ctx, SGN_ESTATE, "a local shard group runs with sgn_run_local_group, not sgn_round");
-  int rc = sync_ctrl(ctx);
-  if (rc) return rc;
-  if (!ctx->h_ctrl->active) return set_error(ctx, SGN_ESTATE, "simulation already finished");
-  if (ctx->h_ctrl->hold && (rc = resolve_hold(ctx))) return rc;  // (an earlier growth failed)
-  if ((rc = launch_round(ctx))) return rc;
-  rc = sync_ctrl(ctx);
-  if (!rc && ctx->h_ctrl->xspill) rc = comm_complete_spill(ctx);
-  if (!rc) rc = resolve_hold(ctx);
-  if (min_next) *min_next = ctx->h_ctrl->last_min_next;
-  return rc;
-}
-
-int sgn_run(sgn_ctx* ctx, uint64_t max_rounds, uint64_t* rounds_done) {
-  if (!ctx || !ctx->sim_ready) return ctx ? set_error(ctx, SGN_ESTATE, "no simulation") : SGN_EINVAL;
-  if (int e = rng_release(ctx)) return e;
-  if (ctx->comm_local)
-    return set_error(ctx, SGN_ESTATE, "a local shard group runs with sgn_run_local_group, not sgn_run");
-  // (the control block as the last sgn_run left it, unless a call since may have changed it)
-  int rc = ctx->ctrl_fresh ? 0 : sync_ctrl(ctx);
-  ctx->ctrl_fresh = false;
-  if (rc) return rc;
-  // a round still held (an earlier pool growth failed and the caller runs again): grow first
-  if ((ctx->h_ctrl->hold || ctx->h_ctrl->spill_n) && (rc = resolve_hold(ctx))) return rc;
-  // (sgn_run_until: a round edge at or past Ctrl::pause_at holds with HOLD_PAUSE and the loops
-  // below stop on it; sgn_run itself runs with pause_at = EMU_MAX and never sees one)
-  ctx->paused = false;
-  const uint64_t r_start = ctx->h_ctrl->rounds;
-  uint64_t enq = 0;
-  // Rounds are enqueued in batches with one host synchronisation per batch (the window
-  // lives on the device; kernels of rounds past the end return at once). On a single
-  // shard a full batch is one hipGraph replay: the round's launches are captured once.
-  const uint64_t batch = 32;
-  // SGN_GRAPH=1: a full batch is captured once as a hipGraph and replayed (multi-shard over
-  // RCCL too: each round's k_execute, the grouped send/recv — RCCL records its kernels in the
-  // graph — and k_import). Off by default: measured on config C with per-round launches,
-  // replays are no faster than eager launches (38.9 vs 38.9 us per round untimed), and the
-  // event-record nodes that time a sample of the rounds slow the replay (1.35 vs 1.47 G
-  // packet events/s); the host enqueues eager rounds faster than the GPU runs them.
-  const bool graph = ctx->use_graph && (ctx->nranks == 1 || ctx->comm) &&
-                     getenv("SGN_GRAPH") && atoi(getenv("SGN_GRAPH")) == 1;
-  if (ctx->nranks == 1 && ctx->persist_grid) {
-    bool fresh = true;
-    // persistent rounds: one launch runs up to kPersistRounds rounds (grid barriers inside);
-    // a launch ends early at a held round edge (a pool grows here, then the rounds go on)
-    while (ctx->h_ctrl->active && enq < max_rounds && ctx->persist_grid && !ctx->paused) {
-      const uint32_t n = (uint32_t)std::min<uint64_t>(kPersistRounds, max_rounds - enq);
-      // (no per-launch memsets: the launch resets its round buffers before its census)
-      time_begin(ctx, K_EXECUTE);
-      launch_k_rounds(ctx, n);
-      time_end(ctx);
-      ctx->kt[K_EXECUTE].total++;
-      SGN_HIP(ctx, hipGetLastError());
-      if ((rc = sync_ctrl_persist(ctx, ctx->res_epoch))) return rc;
-      if (census_verdict(ctx, ctx->res_epoch) != 1) {
-        // the grid was not resident (the occupancy model was wrong, or another context holds
-        // part of the GPU): nothing ran; continue with one launch per round
-        ctx->persist_grid = 0;
-        ctx->persist_fallbacks++;
-        ctx->persist_off = true;
-        break;
-      }
-      if (ctx->h_ctrl->hold || ctx->h_ctrl->spill_n) fresh = false;  // (the host grows a pool)
-      if ((rc = resolve_hold(ctx))) return rc;
-      enq = ctx->h_ctrl->rounds - r_start;
-    }
-    if (!ctx->persist_grid) {
-      uint64_t more = 0;
-      rc = sgn_run(ctx, max_rounds - enq, &more);
-      if (rounds_done) *rounds_done = ctx->h_ctrl->rounds - r_start;
-      return rc;
-    }
-    if (rounds_done) *rounds_done = ctx->h_ctrl->rounds - r_start;
-    ctx->ctrl_fresh = fresh;
-    return 0;
-  }
-  // multi-shard, one shard per GPU: persistent rounds with the peers' inboxes mapped into this
-  // process (k_rounds_x; mapped at the first run, a collective over RCCL), unless refused — then
-  // per-round launches with the RCCL send/recv for the rest
-  if (ctx->nranks > 1 && ctx->comm && xpersist_possible(ctx)) {
-    if (!ctx->x_mapped && (rc = comm_xpeer_map(ctx))) return rc;
-    if (ctx->x_mapped) {
-      uint64_t k = 0;
-      if ((rc = run_xpersist({ctx}, true, max_rounds, &k))) return rc;
-      if (!ctx->x_off || k >= max_rounds || !ctx->h_ctrl->active) {
-        if (rounds_done) *rounds_done = ctx->h_ctrl->rounds - r_start;
-        return 0;
-      }
-    }
-  }
-  // rounds are counted as they complete: a multi-shard round held for a full-slot exchange
-  // (comm_complete_spill) turns the rest of its batch into no-ops, which are not rounds
-  uint64_t done = ctx->h_ctrl->rounds - r_start;
-  static const bool dbg = getenv("SGN_DEBUG_RUN") != nullptr;
-  while (ctx->h_ctrl->active && done < max_rounds && !ctx->paused) {
-    const uint64_t n = std::min<uint64_t>(batch, max_rounds - done);
-    if (dbg)
-      fprintf(stderr, "[sgn r%u] batch n=%llu done=%llu graph=%d gexec=%d gsz=%u xsz=%u spills=%llu\n", ctx->rank,
-              (unsigned long long)n, (unsigned long long)done, (int)graph, ctx->gexec != nullptr, ctx->gsz,
-              ctx->xsz_cur, (unsigned long long)ctx->x_spills);
-    if (graph && n == batch) {
-      if (ctx->gexec && ctx->gsz != ctx->xsz_cur) drop_graph(ctx);  // the send size changed
-      if (!ctx->gexec) {
-        ctx->ev_pending.clear();
-        ctx->ev_next = 0;
-        ctx->capturing = true;
-        hipError_t e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-        for (uint64_t i = 0; i < n && rc == 0 && e == hipSuccess; i++) rc = launch_round(ctx);
-        hipGraph_t g = nullptr;
-        hipError_t e2 = hipStreamEndCapture(ctx->stream, &g);
-        ctx->capturing = false;
-        if (rc) return rc;
-        if (e != hipSuccess) return hip_fail(ctx, e, "hipStreamBeginCapture");
-        if (e2 != hipSuccess) return hip_fail(ctx, e2, "hipStreamEndCapture");
-        ctx->graph = g;
-        if ((rc = add_timing_nodes(ctx, g))) return rc;
-        SGN_HIP(ctx, hipGraphInstantiate(&ctx->gexec, g, nullptr, nullptr, 0));
-        ctx->gbatch = batch;
-        ctx->gsz = ctx->xsz_cur;
-      }
-      SGN_HIP(ctx, hipGraphLaunch(ctx->gexec, ctx->stream));
-      ctx->kt[K_EXECUTE].total += n;
-      if (ctx->nranks > 1) ctx->kt[K_IMPORT].total += n;
-      ctx->graph_pending = !ctx->graph_timed.empty();
-      ctx->x_bytes += n * comm_round_bytes(ctx);
-    } else {
-      for (uint64_t i = 0; i < n; i++)
-        if ((rc = launch_round(ctx))) return rc;
-    }
-    if ((rc = sync_ctrl(ctx))) return rc;
-    if (dbg)
-      fprintf(stderr, "[sgn r%u] synced rounds=%llu spill=%u hwm=%llu\n", ctx->rank,
-              (unsigned long long)(ctx->h_ctrl->rounds - r_start), ctx->h_ctrl->xspill,
-              (unsigned long long)ctx->h_ctrl->xhwm);
-    if (ctx->h_ctrl->xspill && (rc = comm_complete_spill(ctx))) return rc;
-    if ((rc = resolve_hold(ctx))) return rc;
-    if (dbg && ctx->h_ctrl->xspill == 0) fprintf(stderr, "[sgn r%u] after: rounds=%llu\n", ctx->rank,
-                                                 (unsigned long long)(ctx->h_ctrl->rounds - r_start));
-    done = ctx->h_ctrl->rounds - r_start;
-  }
-  if (rounds_done) *rounds_done = ctx->h_ctrl->rounds - r_start;
-  return 0;
-}
-
-int sgn_run_until(sgn_ctx* ctx, uint64_t t_emulated, uint64_t* rounds_done) {
-  if (rounds_done) *rounds_done = 0;
-  if (!ctx) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  if (ctx->nranks > 1 || ctx->comm_local)
-    return set_error(ctx, SGN_ESTATE, "sgn_run_until runs a single shard: a sharded context has no device-side pause "
-                                      "(its round edges are decided across shards)");
-  ctx->ctrl_fresh = false;
-  int rc = sync_ctrl(ctx);
-  if (rc) return rc;
-  // (the fork's rule, manager.rs:1372-1382: pause once min_next_event_time >= target — the window
-  // start IS that minimum, so a target at or below it pauses before anything runs)
-  if (!ctx->h_ctrl->active || t_emulated <= ctx->h_ctrl->ws) return 0;
-  // the round edges compare on the device (finalize_fused, k_rounds): no single-stepping, one
-  // persistent launch still runs many rounds and ends at the first edge at or past the target
-  SGN_HIP(ctx, hipMemcpy((char*)ctx->S.ctrl + offsetof(Ctrl, pause_at), &t_emulated, 8, hipMemcpyHostToDevice));
-  rc = sgn_run(ctx, ~0ull, rounds_done);
-  const uint64_t never = EMU_MAX;
-  const hipError_t e = hipMemcpy((char*)ctx->S.ctrl + offsetof(Ctrl, pause_at), &never, 8, hipMemcpyHostToDevice);
-  ctx->h_ctrl->pause_at = never;
-  ctx->paused = false;
-  if (!rc && e != hipSuccess) rc = hip_fail(ctx, e, "hipMemcpy(pause_at)");
-  return rc;
-}
-
-namespace {
-// the records of owned hosts [off, off + n) (device -> host)
-int read_recs(sgn_ctx* ctx, uint32_t off, uint32_t n, std::vector<HostRec>* out) {
-  out->resize(n);
-  if (n) SGN_HIP(ctx, hipMemcpy(out->data(), (const void*)(ctx->S.hrec + off), (size_t)n * sizeof(HostRec),
-                                hipMemcpyDeviceToHost));
-  if (n && ctx->S.htile) {  // the hot lines from their tiles
-    const uint32_t t0 = off >> 6, t1 = (off + n + 63) >> 6;
-    std::vector<uint64_t> tile((size_t)(t1 - t0) * 8 * 64 * 2);
-    SGN_HIP(ctx, hipMemcpy(tile.data(), (const void*)(ctx->S.htile + (size_t)t0 * 8 * 64 * 2), tile.size() * 8,
-                           hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; i++)
-      for (uint32_t c = 0; c < 8; c++)
-        std::memcpy((char*)&(*out)[i] + 16 * c, &tile[2 * (hot_idx(off + i, c) - (size_t)t0 * 8 * 64)], 16);
-  }
-  return 0;
-}
-// the per-host totals of owned slots [off, off + n): N_CNT rows, then the CoDel maxima
-int read_counts(sgn_ctx* ctx, uint32_t off, uint32_t n, std::vector<uint64_t>* cnt, std::vector<uint32_t>* mq) {
-  const size_t nH = ctx->S.nH;
-  cnt->assign((size_t)N_CNT * n, 0);
-  if (mq) mq->assign(n, 0);
-  if (!n) return 0;
-  if (ctx->S.tkind != SGN_TRAFFIC_PERIODIC) {  // (these kinds keep them in the cold lines)
-    std::vector<HostRec> recs;
-    if (int e = read_recs(ctx, off, n, &recs)) return e;
-    for (uint32_t i = 0; i < n; i++) {
-      (*cnt)[(size_t)N_SENT * n + i] = recs[i].n_sent;
-      (*cnt)[(size_t)N_POPPED * n + i] = recs[i].n_popped;
-      (*cnt)[(size_t)N_DELIVERED * n + i] = recs[i].n_delivered;
-      if (mq) (*mq)[i] = recs[i].max_codel;
-    }
-    return 0;
-  }
-  for (int k = 0; k < N_CNT; k++)
-    SGN_HIP(ctx, hipMemcpy(cnt->data() + (size_t)k * n, (const void*)(ctx->S.n_cnt + k * nH + off), (size_t)n * 8,
-                           hipMemcpyDeviceToHost));
-  if (mq) SGN_HIP(ctx, hipMemcpy(mq->data(), (const void*)(ctx->S.maxq + off), (size_t)n * 4, hipMemcpyDeviceToHost));
-  return 0;
-}
-// the cold lines hold the host's queue state (else it is an idle host's: empty queues)
-inline bool cold_valid(const sgn_ctx* ctx, const HostRec& r) {
-  return ctx->S.tkind != SGN_TRAFFIC_PERIODIC || (r.flags & F_COLD);
-}
-}  // namespace
-
-int sgn_stats_get(sgn_ctx* ctx, sgn_stats* out) {
-  if (!ctx || !out) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  int rc = sync_ctrl(ctx);
-  const uint32_t nH = ctx->S.nH;
-  std::vector<HostRec> recs;
-  std::vector<uint64_t> cnt;
-  std::vector<uint32_t> mq;
-  if (int e = read_recs(ctx, 0, nH, &recs)) return e;
-  if (int e = read_counts(ctx, 0, nH, &cnt, &mq)) return e;
-  sgn_stats s{};
-  uint64_t mc = 0;
-  for (uint32_t h = 0; h < nH; h++) {
-    const HostRec& r = recs[h];
-    s.packets_sent += cnt[(size_t)N_SENT * nH + h];
-    s.packets_unknown_dst += r.n_unknown;
-    s.packet_events_popped += cnt[(size_t)N_POPPED * nH + h];
-    s.codel_dropped += r.n_codel;
-    s.delivered += cnt[(size_t)N_DELIVERED * nH + h];
-    s.local_delivered += r.n_local_deliv;
-    s.app_blocked += r.n_blocked;
-    mc = std::max<uint64_t>(mc, mq[h]);
-  }
-  s.rounds = ctx->h_ctrl->rounds;
-  s.min_used_latency_ns = ctx->h_ctrl->min_used;
-  s.max_codel_len = mc;
-
-  {
-    const size_t G = ctx->S.G;
-    std::vector<uint64_t> wc(W_N * G);
-    SGN_HIP(ctx, hipMemcpy(wc.data(), (const void*)ctx->S.w_cnt, wc.size() * 8, hipMemcpyDeviceToHost));
-    uint64_t acc[W_N] = {};
-    for (int k = 0; k < W_N; k++)
-      for (size_t g = 0; g < G; g++)
-        acc[k] = k == W_MAXFILL ? std::max(acc[k], wc[k * G + g]) : acc[k] + wc[k * G + g];
-    s.max_pending_events = acc[W_MAXFILL];
-    s.host_executions = acc[W_EXEC];
-    s.event_runs = acc[W_RUNS];
-    s.sched_sorted_segments = acc[W_SORTED];
-    s.packets_loss_dropped = acc[W_LOSS];
-    s.local_events = acc[W_LOCAL_EV];
-    s.bytes_delivered = acc[W_BYTES];
-  }
-  s.sched_heavy_hosts = 0;
-  *out = s;
-  return rc;
-}
-
-int sgn_host_digests(sgn_ctx* ctx, uint32_t lo, uint32_t hi, sgn_host_digest* out) {
-  if (!ctx || !out) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  if (lo < ctx->lo || hi > ctx->hi || lo > hi) return set_error(ctx, SGN_EINVAL, "range outside the owned shard");
-  if (int e = rng_release(ctx)) return e;
-  int rc = sync_ctrl(ctx);
-  const uint32_t n = hi - lo;
-  // the range's hosts sit in permuted slots: read the slots they span
-  uint32_t smin = ctx->hi, smax = ctx->lo;
-  for (uint32_t i = lo; i < hi; i++) {
-    smin = std::min(smin, ctx->sid_of[i]);
-    smax = std::max(smax, ctx->sid_of[i]);
-  }
-  std::vector<HostRec> recs;
-  std::vector<uint64_t> cnt;
-  const uint32_t ns = n ? smax - smin + 1 : 0;
-  if (n) {
-    if (int e = read_recs(ctx, smin - ctx->lo, ns, &recs)) return e;
-    if (int e = read_counts(ctx, smin - ctx->lo, ns, &cnt, nullptr)) return e;
-  }
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t j = ctx->sid_of[lo + i] - smin;
-    const HostRec& r = recs[j];
-    sgn_host_digest& o = out[i];
-    o.tx = r.dig[0];
-    o.rx = r.dig[1];
-    o.app = r.dig[2];
-    for (int k = 0; k < 4; k++) o.rng[k] = r.rng[k];
-    o.next_event_id = r.eid;
-    o.n_sent = cnt[(size_t)N_SENT * ns + j];
-    o.n_popped = cnt[(size_t)N_POPPED * ns + j];
-    o.n_delivered = cnt[(size_t)N_DELIVERED * ns + j];
-    o.n_codel_dropped = r.n_codel;
-  }
-  return rc;
-}
-
-namespace {
-// Host::next_event_time for owned HostIds [lo, hi): two small kernels, one copy.
-int next_event_times(sgn_ctx* ctx, uint32_t lo, uint32_t hi, uint64_t* out) {
-  if (!ctx || (!out && hi > lo)) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  if (lo < ctx->lo || hi > ctx->hi || lo > hi) return set_error(ctx, SGN_EINVAL, "host range not owned by this shard");
-  int rc = sync_ctrl(ctx);
-  if (rc) return rc;
-  const uint32_t n = hi - lo;
-  if (n == 0) return 0;
-  const DevSim& S = ctx->S;
-  SGN_HIP(ctx, hipSetDevice(ctx->device));
-  uint64_t* d = nullptr;
-  SGN_HIP(ctx, hipMalloc(&d, (size_t)n * 8));
-  // the groups holding the range's slots: one host's group, or all of them
-  uint32_t g0 = 0, ng = S.G;
-  if (n == 1) {
-    g0 = (ctx->sid_of[lo] - ctx->lo) >> S.gsh;
-    ng = 1;
-  }
-  hipLaunchKernelGGL(k_next_local, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const DevSim*)ctx->d_S, lo, n, d);
-  hipLaunchKernelGGL(k_next_packet, dim3(S.NB * ng), dim3(64), 0, ctx->stream, (const DevSim*)ctx->d_S, lo, n, g0,
-                     ng, d);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(d);
-  if (e != hipSuccess) return hip_fail(ctx, e, "next event times");
-  return 0;
-}
-}  // namespace
-
-int sgn_host_next_event_time(sgn_ctx* ctx, uint32_t host, uint64_t* t) {
-  if (!ctx || !t) return SGN_EINVAL;
-  return next_event_times(ctx, host, host + 1, t);
-}
-
-int sgn_hosts_next_event_time(sgn_ctx* ctx, uint32_t host_lo, uint32_t host_hi, uint64_t* out) {
-  return next_event_times(ctx, host_lo, host_hi, out);
-}
-
-int sgn_trace_read(sgn_ctx* ctx, sgn_trace_rec* out, uint64_t cap, uint64_t* n_total) {
-  if (!ctx) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  int rc = sync_ctrl(ctx);
-  const uint64_t n = std::min<uint64_t>(ctx->h_ctrl->trace_n, ctx->S.trace_cap);
-  if (n_total) *n_total = ctx->h_ctrl->trace_n;
-  const uint64_t k = std::min(n, cap);
-  if (k && out) SGN_HIP(ctx, hipMemcpy(out, ctx->S.trace, k * sizeof(sgn_trace_rec), hipMemcpyDeviceToHost));
-  return rc;
-}
-
-int sgn_engine_info_get(sgn_ctx* ctx, sgn_engine_info* out) {
-  if (!ctx || !out) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  const DevSim& S = ctx->S;
-  out->calendar_buckets = S.NB;
-  out->bucket_width_ns = S.BW;
-  out->host_groups = S.G;
-  out->slab_capacity = S.CAP;
-  out->hosts_per_wave = 1u << S.gsh;
-  out->persistent_grid = ctx->persist_grid;
-  out->persistent_fallbacks = ctx->persist_fallbacks;
-  out->device_bytes = ctx->sim_bytes;
-  out->exchange_slot_runs = ctx->nranks > 1 ? ctx->xslot : 0;
-  out->exchange_send_runs = ctx->xsz_cur;
-  out->exchange_hwm_runs = ctx->h_ctrl ? ctx->h_ctrl->xhwm : 0;
-  out->exchange_spills = ctx->x_spills;
-  out->exchange_bytes = ctx->x_bytes;
-  out->codel_pages = ctx->S.cq_pages;
-  // the control block as is (an overflow is reported by the calls that run rounds, not here)
-  SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  SGN_HIP(ctx, hipMemcpy(ctx->h_ctrl, (const void*)ctx->S.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
-  const Ctrl& c = *ctx->h_ctrl;
-  out->codel_page_allocs = ctx->codel_allocs_before + c.pg_alloc;
-  out->codel_pages_free = c.pg_tail >= c.pg_alloc ? c.pg_tail - c.pg_alloc : 0;
-  std::vector<HostRec> recs;
-  if (int e = read_recs(ctx, 0, ctx->S.nH, &recs)) return e;
-  uint64_t chained = 0;
-  for (const HostRec& r : recs) {
-    const uint32_t nr = cold_valid(ctx, r) ? r.cq_nr : 0;
-    chained += nr == 0 ? 1 : ((r.cq_head & (CQ_PAGE - 1)) + nr + CQ_PAGE - 1) / CQ_PAGE;
-  }
-  out->codel_pages_chained = chained;
-  int ncu = 0;
-  SGN_HIP(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  out->compute_units = (uint64_t)ncu;
-  out->bucket_min_lds = ctx->S.agg_bmin;
-  out->lds_per_cu = ctx->lds_per_cu;
-  out->codel_pool_grows = ctx->codel_grows;
-  out->calendar_grows = ctx->cal_grows;
-  out->calendar_spill_runs = ctx->cal_spill_runs;
-  out->exchange_slot_grows = ctx->xslot_grows;
-  out->rounds_held = ctx->rounds_held;
-  out->slab_extensions = ctx->ext_slabs;
-  out->slab_extension_runs = ctx->S.ext_total;
-  {
-    const size_t G = ctx->S.G;
-    std::vector<uint64_t> wb(G);
-    SGN_HIP(ctx, hipMemcpy(wb.data(), (const void*)(ctx->S.w_cnt + W_BIG * G), G * 8, hipMemcpyDeviceToHost));
-    uint64_t t = 0;
-    for (uint64_t v : wb) t += v;
-    out->big_slab_pieces = t;
-  }
-  out->spill_area_runs = ctx->S.spill_cap;
-  out->spill_area_grows = ctx->spill_grows;
-  out->exchange_mode = ctx->nranks > 1 ? ctx->x_mode : 0;
-  out->inbox_slot_runs = ctx->nranks > 1 ? ctx->S.xislot : 0;
-  out->inbox_grows = ctx->x_grows;
-  out->inbox_overflow_rounds = ctx->x_over_rounds;
-  out->inbox_moved_runs = ctx->x_moved;
-  out->persistent_x_launches = ctx->x_launches;
-  out->persistent_x_grid = ctx->x_grid;
-  return 0;
-}
-
-int sgn_kernel_times_get(sgn_ctx* ctx, sgn_kernel_times* out) {
-  if (!ctx || !out) return SGN_EINVAL;
-  if (ctx->sim_ready) {
-    int rc = sync_ctrl(ctx);
-    if (rc) return rc;
-  }
-  std::memset(out, 0, sizeof(*out));
-  out->n_kernels = K_NUM;
-  for (int i = 0; i < K_NUM; i++) {
-    out->launches[i] = ctx->kt[i].launches;
-    out->launches_total[i] = ctx->kt[i].total;
-    out->ms[i] = ctx->kt[i].ms;
-    out->name[i] = kKernelNames[i];
-  }
-  // the round kernel's slot: persistent launches (many rounds each) when enabled
-  if (ctx->persist_grid) out->name[K_EXECUTE] = "k_rounds";
-  if (ctx->x_mode == 2) out->name[K_EXECUTE] = "k_rounds_x";
-  return 0;
-}
-
-// Diagnostics: per-wave {cycles, events, max lane events, busy lanes} of the last k_execute
-// (allocated when SGN_STAMPS=1 is set in the environment at sgn_sim_init).
-// Diagnostics of the last persistent launch (SGN_STAMPS=2): per round {earliest start, latest
-// arrival, round edge done} (100 MHz clock), 128 rounds; resets the buffer for the next launch.
-int sgn_debug_rounds(sgn_ctx* ctx, uint64_t* out) {
-  if (!ctx || !ctx->sim_ready || !ctx->S.rdbg) return SGN_EINVAL;
-  SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  SGN_HIP(ctx, hipMemcpy(out, (const void*)ctx->S.rdbg, 3 * 128 * 8, hipMemcpyDeviceToHost));
-  std::vector<uint64_t> init(3 * 128, 0);
-  for (int r = 0; r < 128; r++) init[3 * r] = ~0ULL;
-  SGN_HIP(ctx, hipMemcpy((void*)ctx->S.rdbg, init.data(), init.size() * 8, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// The same for k_rounds_x: per round 8 words (see the kernel's stamps), 128 rounds; resets.
-int sgn_debug_rounds_x(sgn_ctx* ctx, uint64_t* out) {
-  if (!ctx || !ctx->sim_ready || !ctx->S.rdbg) return SGN_EINVAL;
-  SGN_HIP(ctx, hipDeviceSynchronize());
-  SGN_HIP(ctx, hipMemcpy(out, (const void*)ctx->S.rdbg, 8 * 128 * 8, hipMemcpyDeviceToHost));
-  std::vector<uint64_t> init(8 * 128, 0);
-  for (int r = 0; r < 128; r++) init[8 * r] = ~0ULL;
-  SGN_HIP(ctx, hipMemcpy((void*)ctx->S.rdbg, init.data(), init.size() * 8, hipMemcpyHostToDevice));
-  return 0;
-}
-
-// k_rounds_x with SGN_STAMPS=3: every workgroup's stamps, [128 rounds][2048 workgroups][8]
-// (this shard's workgroup index; unwritten: 0); resets.
-int sgn_debug_rounds_xw(sgn_ctx* ctx, uint64_t* out) {
-  if (!ctx || !ctx->sim_ready || !ctx->S.rdbg || !ctx->S.rdbg_wg) return SGN_EINVAL;
-  const size_t n = (size_t)8 * 128 * 2048;
-  SGN_HIP(ctx, hipDeviceSynchronize());
-  SGN_HIP(ctx, hipMemcpy(out, (const void*)ctx->S.rdbg, n * 8, hipMemcpyDeviceToHost));
-  SGN_HIP(ctx, hipMemset((void*)ctx->S.rdbg, 0, n * 8));
-  return 0;
-}
-
-int sgn_debug_stamps(sgn_ctx* ctx, uint64_t* out, uint64_t cap, uint64_t* n) {
-  if (!ctx || !ctx->sim_ready) return SGN_EINVAL;
-  const uint64_t waves = ctx->S.G;
-  if (n) *n = ctx->S.stamps ? waves : 0;
-  if (!ctx->S.stamps || !out) return 0;
-  SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  SGN_HIP(ctx, hipMemcpy(out, ctx->S.stamps, std::min(cap, waves) * SGN_STAMP_WORDS * 8, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// ---- CPU-resident applications (SGN_TRAFFIC_EXTERNAL) ----
-int sgn_drain_enable(sgn_ctx* ctx, uint64_t capacity) {
-  if (!ctx) return SGN_EINVAL;
-  if (ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "sgn_drain_enable must precede sgn_sim_init");
-  if (capacity == 0) return set_error(ctx, SGN_EINVAL, "drain capacity must be >= 1");
-  ctx->drain_cap = capacity;
-  return 0;
-}
-
-int sgn_submit(sgn_ctx* ctx, const sgn_pkt_soa* b) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  if (!ctx || !b) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  const DevSim& S = ctx->S;
-  if (S.tkind != SGN_TRAFFIC_EXTERNAL)
-    return set_error(ctx, SGN_ESTATE, "sgn_submit needs SGN_TRAFFIC_EXTERNAL traffic");
-  if (b->n == 0) return 0;
-  if (!b->src_host || !b->dst_ip || !b->payload_len || !b->send_time)
-    return set_error(ctx, SGN_EINVAL, "sgn_submit: missing array");
-  int rc = sync_ctrl(ctx);
-  if (rc) return rc;
-  const uint64_t ws = ctx->h_ctrl->ws;
-  // the calendar holds NB buckets of BW ns; the gather walks forward from the window
-  const uint64_t horizon = ws + (uint64_t)(S.NB - 2) * S.BW;
-  if (ctx->handles.size() + b->n > SGN_TAG_SLOT_MASK)
-    return set_error(ctx, SGN_ERANGE, "more than 2^29 submissions on one shard");
-  std::vector<EvRec> recs(b->n);
-  std::vector<uint32_t> seq_add;
-  std::vector<uint32_t> seq = ctx->submit_seq;  // committed only on success
-  for (uint64_t i = 0; i < b->n; i++) {
-    const uint32_t src = b->src_host[i];
-    const uint64_t t = b->send_time[i];
-    const uint32_t pay = b->payload_len[i];
-    if (src < ctx->lo || src >= ctx->hi)
-      return set_error(ctx, SGN_EINVAL, "sgn_submit: source host " + std::to_string(src) + " not owned by this shard");
-    if (t < ws || t >= S.end_time)
-      return set_error(ctx, SGN_EINVAL, "sgn_submit: send_time outside [window start, stop time)");
-    if (t >= horizon)
-      return set_error(ctx, SGN_EINVAL, "sgn_submit: send_time beyond the event calendar's horizon; submit it closer to its window");
-    if (pay > 0xFFFFu) return set_error(ctx, SGN_EINVAL, "sgn_submit: payload_len > 65535");
-    uint32_t hdr = 0;
-    if (b->wire_len && b->wire_len[i] != 0) {
-      const uint32_t w = b->wire_len[i];
-      if (w == pay + SGN_UDP_HEADER_BYTES) hdr = 0;
-      else if (w == pay + SGN_TCP_HEADER_BYTES) hdr = SGN_TAG_HDR_TCP;
-      else if (w == pay + SGN_TCP_WS_HEADER_BYTES) hdr = SGN_TAG_HDR_TCPWS;
-      else
-        return set_error(ctx, SGN_EINVAL,
-                         "sgn_submit: wire_len must be payload_len + 28 (UDP/IPv4), + 40 or + 44 (TCP/IPv4)");
-    }
-    uint32_t& q = seq[src - ctx->lo];
-    if (q == 0xFFFFFFFFu) return set_error(ctx, SGN_ERANGE, "sgn_submit: 2^32 submissions from one host");
-    EvRec& r = recs[i];
-    r.time = t;
-    r.eid = ((uint64_t)q++ << 32) | b->dst_ip[i];  // submission order, then the address
-    r.src = src;
-    r.dst = ctx->sid_of[src];  // filed in the source's own slot
-    r.pc = pay | (1u << 16);
-    r.tag = SGN_TAG_EXT | hdr | (uint32_t)(ctx->handles.size() + i);
-  }
-  SGN_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->stage_cap < b->n) {
-    if (ctx->d_stage) hipFree(ctx->d_stage);
-    ctx->d_stage = nullptr;
-    ctx->stage_cap = 0;
-    SGN_HIP(ctx, hipMalloc(&ctx->d_stage, b->n * sizeof(EvRec)));
-    ctx->stage_cap = b->n;
-  }
-  SGN_HIP(ctx, hipMemcpyAsync(ctx->d_stage, recs.data(), b->n * sizeof(EvRec), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_inject, dim3((uint32_t)((b->n + 255) / 256)), dim3(256), 0, ctx->stream,
-                     (const DevSim*)ctx->d_S, (const EvRec*)ctx->d_stage, (uint32_t)b->n);
-  SGN_HIP(ctx, hipGetLastError());
-  // the runs are in the device calendar from here: a failure past this point leaves them there
-  // with no handle, so the context is marked unusable (a retry would file them twice)
-  rc = sync_ctrl(ctx);
-  if (!rc && ctx->h_ctrl->spill_n) rc = relayout_calendar(ctx);
-  if (rc) {
-    ctx->failed = std::string("sgn_submit failed after filing its runs: ") + sgn_last_error(ctx);
-    return rc;
-  }
-  for (uint64_t i = 0; i < b->n; i++) ctx->handles.push_back(b->handle ? b->handle[i] : 0);
-  ctx->submit_seq.swap(seq);
-  return 0;
-}
-
-// ---- per-thread staging: stages are plain host buffers; one flush submits all
-int sgn_stage_create(sgn_ctx* ctx, sgn_stage** out) {
-  if (!ctx || !out) return SGN_EINVAL;
-  sgn_stage* st = new sgn_stage();
-  st->ctx = ctx;
-  std::lock_guard<std::mutex> g(ctx->stage_mu);
-  ctx->stages.push_back(st);
-  *out = st;
-  return 0;
-}
-
-void sgn_stage_destroy(sgn_stage* st) {
-  if (!st) return;
-  if (st->ctx) {
-    std::lock_guard<std::mutex> g(st->ctx->stage_mu);
-    auto& v = st->ctx->stages;
-    v.erase(std::remove(v.begin(), v.end(), st), v.end());
-  }
-  delete st;
-}
-
-int sgn_stage_push(sgn_stage* st, const sgn_pkt_soa* b) {
-  if (!st || !b) return SGN_EINVAL;
-  if (b->n == 0) return 0;
-  if (!b->src_host || !b->dst_ip || !b->payload_len || !b->send_time) return SGN_EINVAL;
-  for (uint64_t i = 0; i < b->n; i++) {
-    if (b->payload_len[i] > 0xFFFFu) return SGN_EINVAL;
-    if (b->wire_len && b->wire_len[i] != 0) {
-      const uint32_t w = b->wire_len[i], p = b->payload_len[i];
-      if (w != p + SGN_UDP_HEADER_BYTES && w != p + SGN_TCP_HEADER_BYTES && w != p + SGN_TCP_WS_HEADER_BYTES)
-        return SGN_EINVAL;
-    }
-  }
-  std::lock_guard<std::mutex> g(st->mu);  // (uncontended except against a concurrent flush)
-  st->src.insert(st->src.end(), b->src_host, b->src_host + b->n);
-  st->dst.insert(st->dst.end(), b->dst_ip, b->dst_ip + b->n);
-  st->pay.insert(st->pay.end(), b->payload_len, b->payload_len + b->n);
-  st->time.insert(st->time.end(), b->send_time, b->send_time + b->n);
-  for (uint64_t i = 0; i < b->n; i++) st->handle.push_back(b->handle ? b->handle[i] : 0);
-  for (uint64_t i = 0; i < b->n; i++) st->wire.push_back(b->wire_len ? b->wire_len[i] : 0);
-  return 0;
-}
-
-uint64_t sgn_stage_pending(const sgn_stage* st) {
-  if (!st) return 0;
-  std::lock_guard<std::mutex> g(st->mu);
-  return st->src.size();
-}
-
-int sgn_stage_flush(sgn_ctx* ctx) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  if (!ctx) return SGN_EINVAL;
-  std::vector<uint32_t> src, dst, pay, wire;
-  std::vector<uint64_t> time, handle;
-  // each stage's size at copy time: only that prefix is cleared after the submit, so a push
-  // that lands while the flush runs stays staged for the next flush
-  std::vector<std::pair<sgn_stage*, size_t>> taken;
-  {
-    std::lock_guard<std::mutex> g(ctx->stage_mu);
-    for (sgn_stage* st : ctx->stages) {
-      std::lock_guard<std::mutex> sg(st->mu);
-      taken.push_back({st, st->src.size()});
-      wire.insert(wire.end(), st->wire.begin(), st->wire.end());
-      src.insert(src.end(), st->src.begin(), st->src.end());
-      dst.insert(dst.end(), st->dst.begin(), st->dst.end());
-      pay.insert(pay.end(), st->pay.begin(), st->pay.end());
-      time.insert(time.end(), st->time.begin(), st->time.end());
-      handle.insert(handle.end(), st->handle.begin(), st->handle.end());
-    }
-  }
-  if (src.empty()) return 0;
-  sgn_pkt_soa b{src.size(), src.data(), dst.data(), pay.data(), wire.data(), time.data(), handle.data()};
-  if (int rc = sgn_submit(ctx, &b)) return rc;
-  std::lock_guard<std::mutex> g(ctx->stage_mu);
-  for (auto& t : taken) {
-    sgn_stage* st = t.first;
-    if (std::find(ctx->stages.begin(), ctx->stages.end(), st) == ctx->stages.end()) continue;  // destroyed meanwhile
-    std::lock_guard<std::mutex> sg(st->mu);
-    const size_t k = t.second;
-    st->src.erase(st->src.begin(), st->src.begin() + k);
-    st->dst.erase(st->dst.begin(), st->dst.begin() + k);
-    st->pay.erase(st->pay.begin(), st->pay.begin() + k);
-    st->time.erase(st->time.begin(), st->time.begin() + k);
-    st->handle.erase(st->handle.begin(), st->handle.begin() + k);
-    st->wire.erase(st->wire.begin(), st->wire.begin() + k);
-  }
-  return 0;
-}
-
-int sgn_drain(sgn_ctx* ctx, uint32_t lo, uint32_t hi, sgn_drain_rec* out, uint64_t cap, uint64_t* n_out) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  if (!ctx || (!out && cap)) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  if (ctx->S.tkind != SGN_TRAFFIC_EXTERNAL)
-    return set_error(ctx, SGN_ESTATE, "sgn_drain needs SGN_TRAFFIC_EXTERNAL traffic");
-  int rc = sync_ctrl(ctx);
-  if (rc) return rc;
-  const uint64_t n = ctx->h_ctrl->drain_n;
-  if (n) {
-    const size_t old = ctx->drain_held.size();
-    ctx->drain_held.resize(old + n);
-    SGN_HIP(ctx, hipMemcpy(ctx->drain_held.data() + old, (const void*)ctx->S.drain, n * sizeof(sgn_drain_rec),
-                           hipMemcpyDeviceToHost));
-    const uint64_t zero = 0;
-    SGN_HIP(ctx, hipMemcpy((char*)ctx->S.ctrl + offsetof(Ctrl, drain_n), &zero, 8, hipMemcpyHostToDevice));
-    ctx->h_ctrl->drain_n = 0;
-    for (size_t i = old; i < ctx->drain_held.size(); i++) {
-      sgn_drain_rec& r = ctx->drain_held[i];
-      const uint32_t slot = r.tag & SGN_TAG_SLOT_MASK;
-      // a slot is this shard's when the datagram's source is one of its hosts
-      r.handle = ((r.tag & SGN_TAG_EXT) && r.src_host >= ctx->lo && r.src_host < ctx->hi &&
-                  slot < ctx->handles.size()) ? ctx->handles[slot] : 0;
-    }
-  }
-  std::vector<sgn_drain_rec> sel, keep;
-  for (const sgn_drain_rec& r : ctx->drain_held) (r.host >= lo && r.host < hi ? sel : keep).push_back(r);
-  auto key = [](const sgn_drain_rec& r) {
-    return std::make_tuple(r.host, r.time, r.src_host, r.src_eid, r.tag, r.status);
-  };
-  std::sort(sel.begin(), sel.end(), [&](const sgn_drain_rec& a, const sgn_drain_rec& b) { return key(a) < key(b); });
-  const uint64_t k = std::min<uint64_t>(cap, sel.size());
-  if (k) std::memcpy(out, sel.data(), k * sizeof(sgn_drain_rec));
-  keep.insert(keep.end(), sel.begin() + k, sel.end());
-  ctx->drain_held.swap(keep);
-  if (n_out) *n_out = k;
-  return 0;
-}
-
-int sgn_set_window(sgn_ctx* ctx, uint64_t start, uint64_t end) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  if (!ctx) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  int rc = sync_ctrl(ctx);
-  if (rc) return rc;
-  Ctrl& c = *ctx->h_ctrl;
-  if (start < c.prev_we) return set_error(ctx, SGN_EINVAL, "sgn_set_window: start before the previous window's end");
-  if (start > c.ws) return set_error(ctx, SGN_EINVAL, "sgn_set_window: start after the device's next event time");
-  if (end <= start) return set_error(ctx, SGN_EINVAL, "sgn_set_window: empty window");
-  if (end - start > ctx->S.BW)
-    return set_error(ctx, SGN_EINVAL, "sgn_set_window: window longer than the runahead the calendar was sized for");
-  end = std::min(end, ctx->S.end_time);
-  if (end <= start) return set_error(ctx, SGN_EINVAL, "sgn_set_window: window at or past the stop time");
-  c.ws = start;
-  c.we = end;
-  c.active = 1;
-  SGN_HIP(ctx, hipMemcpy((void*)ctx->S.ctrl, &c, offsetof(Ctrl, overflow), hipMemcpyHostToDevice));
-  // the CoDel guard for the window as set (the last round edge evaluated the one it computed)
-  const uint64_t need = codel_need_host(ctx), have = c.pg_avail > c.pg_alloc ? c.pg_avail - c.pg_alloc : 0;
-  if (have < need) return grow_codel(ctx, need - have);
-  return 0;
-}
-
-
-namespace {
-// rand_xoshiro 0.7.0 Xoshiro256PlusPlus::next_u64 on the CPU (a CPU-held host state)
-inline uint64_t host_xoshiro_next(uint64_t* s) {
-  auto rotl = [](uint64_t x, int k) { return (x << k) | (x >> (64 - k)); };
-  const uint64_t r = rotl(s[0] + s[3], 23) + s[0], t = s[1] << 17;
-  s[2] ^= s[0];
-  s[3] ^= s[1];
-  s[1] ^= s[2];
-  s[0] ^= s[3];
-  s[2] ^= t;
-  s[3] = rotl(s[3], 45);
-  return r;
-}
-// n single draws of one owned host on the CPU: the first draw after a device operation reads
-// the state (one 32-byte copy); later ones are a few nanoseconds each
-int rng_cpu_draws(sgn_ctx* ctx, uint32_t host, uint64_t n, uint64_t* out) {
-  if (!ctx) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  if (host < ctx->lo || host >= ctx->hi) return set_error(ctx, SGN_EINVAL, "host not owned by this shard");
-  const uint32_t slot = ctx->sid_of[host] - ctx->lo;
-  auto it = ctx->rng_held.find(slot);
-  if (it == ctx->rng_held.end()) {
-    sgn_ctx::RngHeld h{};
-    SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->S.htile) {
-      SGN_HIP(ctx, hipMemcpy(h.s, (const void*)(ctx->S.htile + 2 * hot_idx(slot, 0)), 16, hipMemcpyDeviceToHost));
-      SGN_HIP(ctx, hipMemcpy(h.s + 2, (const void*)(ctx->S.htile + 2 * hot_idx(slot, 1)), 16, hipMemcpyDeviceToHost));
-    } else {
-      SGN_HIP(ctx, hipMemcpy(h.s, (const void*)(ctx->S.hrec + slot), 32, hipMemcpyDeviceToHost));
-    }
-    it = ctx->rng_held.emplace(slot, h).first;
-  }
-  for (uint64_t i = 0; i < n; i++) out[i] = host_xoshiro_next(it->second.s);
-  it->second.draws += n;
-  return 0;
-}
-// counts[i] draws from each of n distinct owned hosts, concatenated in order into out
-int rng_draws(sgn_ctx* ctx, const uint32_t* hosts, const uint32_t* counts, uint32_t n, uint64_t* out) {
-  if (!ctx || (n && (!hosts || !counts))) return SGN_EINVAL;
-  if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
-  std::vector<uint32_t> loc(n);
-  std::vector<uint64_t> off(n);
-  uint64_t total = 0;
-  std::vector<uint32_t> seen;
-  for (uint32_t i = 0; i < n; i++) {
-    if (hosts[i] < ctx->lo || hosts[i] >= ctx->hi) return set_error(ctx, SGN_EINVAL, "host not owned by this shard");
-    loc[i] = ctx->sid_of[hosts[i]] - ctx->lo;  // the host's slot
-    off[i] = total;
-    total += counts[i];
-    seen.push_back(hosts[i]);
-  }
-  std::sort(seen.begin(), seen.end());
-  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
-    return set_error(ctx, SGN_EINVAL, "sgn_rng_next_u64_batch: hosts must be distinct");
-  if (total && !out) return SGN_EINVAL;
-  if (n == 0) return 0;
-  if (int rc = rng_release(ctx)) return rc;
-  SGN_HIP(ctx, hipSetDevice(ctx->device));
-  char* d = nullptr;
-  const size_t bytes = (size_t)n * (4 + 4 + 8) + total * 8 + 16;
-  SGN_HIP(ctx, hipMalloc(&d, bytes));
-  uint32_t* dh = (uint32_t*)d;
-  uint32_t* dc = dh + n;
-  uint64_t* doff = (uint64_t*)(d + ((size_t)n * 8 + 7) / 8 * 8);
-  uint64_t* dout = doff + n;
-  hipError_t e = hipMemcpyAsync(dh, loc.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dc, counts, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(doff, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_rng, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, (const DevSim*)ctx->d_S, dh, dc,
-                       doff, n, dout);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && total) e = hipMemcpyAsync(out, dout, total * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(d);
-  if (e != hipSuccess) return hip_fail(ctx, e, "host rng draws");
-  return 0;
-}
-int rng_draw(sgn_ctx* ctx, uint32_t host, uint32_t n, uint64_t* out) {
-  return rng_cpu_draws(ctx, host, n, out);
-}
-}  // namespace
-
-int sgn_rng_next_u64_batch(sgn_ctx* ctx, const uint32_t* hosts, const uint32_t* counts, uint32_t n,
-                           uint64_t* out) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  return rng_draws(ctx, hosts, counts, n, out);
-}
-
-int sgn_rng_next_u64(sgn_ctx* ctx, uint32_t host, uint64_t* out) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  return rng_draw(ctx, host, 1, out);
-}
-
-int sgn_rng_double(sgn_ctx* ctx, uint32_t host, double* out) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  if (!out) return SGN_EINVAL;
-  uint64_t x = 0;
-  int rc = rng_draw(ctx, host, 1, &x);
-  if (rc == 0) *out = (double)(x >> 11) * 0x1.0p-53;
-  return rc;
-}
-
-int sgn_rng_fill_bytes(sgn_ctx* ctx, uint32_t host, uint8_t* buf, size_t len) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  if (!buf && len) return SGN_EINVAL;
-  if (len / 8 + 1 > 0xFFFFFFFFull) return set_error(ctx, SGN_ERANGE, "sgn_rng_fill_bytes: len too large");
-  const size_t full = len / 8, rem = len % 8;
-  std::vector<uint64_t> v(full + (rem ? 1 : 0));
-  int rc = rng_draw(ctx, host, (uint32_t)v.size(), v.data());
-  if (rc) return rc;
-  for (size_t i = 0; i < full; i++)
-    for (int k = 0; k < 8; k++) buf[8 * i + k] = (uint8_t)(v[i] >> (8 * k));
-  if (rem) {
-    // fill_bytes_via_next: 5..7 bytes from next_u64, 1..4 from next_u32 = next_u64 >> 32
-    const uint64_t w = rem > 4 ? v[full] : (v[full] >> 32);
-    for (size_t k = 0; k < rem; k++) buf[8 * full + k] = (uint8_t)(w >> (8 * k));
-  }
-  return 0;
-}
-
-// Test hook: device CoDel control-law increments for count in [0, n).
-int sgn_selftest_codel_law(sgn_ctx* ctx, uint64_t n, uint64_t* out) {
-  if (ctx) ctx->ctrl_fresh = false;  // (it may change the device control block)
-  if (!ctx || !out) return SGN_EINVAL;
-  SGN_HIP(ctx, hipSetDevice(ctx->device));
-  uint64_t* d = nullptr;
-  SGN_HIP(ctx, hipMalloc(&d, n * 8));
-  hipLaunchKernelGGL(k_codel_law_test, dim3(1024), dim3(256), 0, ctx->stream, n, d);
-  hipError_t e = hipMemcpyAsync(out, d, n * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(d);
-  if (e != hipSuccess) return hip_fail(ctx, e, "codel law selftest");
-  return 0;
-}
-
-}  // extern "C"
-
-// hooks used by comm.cpp
-namespace sgn {
-// The CPU-held states go back before anything on the device uses a host RNG (rounds, batch
-// draws, digests): one small upload and one kernel, stream-ordered (no host wait).
-int rng_release(sgn_ctx* ctx) {
-  if (ctx->rng_held.empty() || !ctx->sim_ready) {
-    ctx->rng_held.clear();
-    return 0;
-  }
-  std::vector<uint64_t> st;
-  st.reserve(ctx->rng_held.size() * 6);
-  for (auto& kv : ctx->rng_held) {
-    if (!kv.second.draws) continue;
-    st.push_back(kv.first);
-    for (int k = 0; k < 4; k++) st.push_back(kv.second.s[k]);
-    st.push_back(kv.second.draws);
-  }
-  ctx->rng_held.clear();
-  const uint32_t n = (uint32_t)(st.size() / 6);
-  if (!n) return 0;
-  SGN_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->rng_stage_cap < st.size()) {
-    if (ctx->d_rng_stage) hipFree(ctx->d_rng_stage);
-    ctx->d_rng_stage = nullptr;
-    ctx->rng_stage_cap = 0;
-    SGN_HIP(ctx, hipMalloc(&ctx->d_rng_stage, st.size() * 8));
-    ctx->rng_stage_cap = st.size();
-  }
-  SGN_HIP(ctx, hipMemcpyAsync(ctx->d_rng_stage, st.data(), st.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_rng_set, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, (const DevSim*)ctx->d_S,
-                     (const uint64_t*)ctx->d_rng_stage, n);
-  SGN_HIP(ctx, hipGetLastError());
-  SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vector goes out of scope)
-  return 0;
-}
-
-void launch_execute(sgn_ctx* ctx) { launch_k_execute(ctx, ctx->stream); }
-// k_import files the received runs and its last block advances the window
-void launch_import(sgn_ctx* ctx) {
-  hipLaunchKernelGGL(k_import, dim3(kImportBlocks), dim3(256), 0, ctx->stream, ctx->S);
-  if (!ctx->capturing) ctx->kt[K_IMPORT].total++;
-}
-}  // namespace sgn
-
-uint64_t sgn::layout_sig_engine() { return kLayoutSig; }

@@ -640,6 +640,51 @@ constexpr uint32_t CAP_MIN = 64, CAP_MAX = 1024;
 constexpr uint32_t LDS_BSLAB = 256;  // calendars with up to this many buckets keep their
                                      // bucket -> slab table in k_execute's LDS
 
+// ---- what the kernels (engine.hip) and the host code that sizes and launches them share ----
+constexpr uint32_t GATHER_SPEC = 16;  // slab slots a gather loads before the fill is known
+// The round kernels' dynamic LDS before the optional bucket-minimum table: CAP event runs and
+// two u16 index arrays (padded to 8 bytes), at least 1 KB — a big slab's radix select keeps its
+// 256-bin histogram there (exec_group), and test hooks may set CAP below 32
+__host__ __device__ __forceinline__ size_t exec_lds_runs_bytes(uint32_t cap) {
+  const size_t b = (size_t)cap * sizeof(EvRec) + 2 * (size_t)((cap + 3) & ~3u) * 2;
+  return b > 1024 ? b : 1024;
+}
+// dynamic LDS of k_execute / k_rounds: CAP event runs + two u16 index arrays
+// (the u16 index arrays are padded to 8 bytes so the optional bucket-minimum table that
+// follows them is aligned)
+inline size_t exec_lds_bytes(uint32_t cap, uint32_t agg_nb = 0) {
+  return exec_lds_runs_bytes(cap) + (agg_nb ? (size_t)(agg_nb + 1) * 4 : 0);
+}
+
+// The CoDel pages a round over [ws, we) may take. A page is taken only when a CoDel push
+// opens a new run on a full tail page (codel_push_run), and every push is one due event run:
+// a host receiving k runs takes at most ceil(k / 16) pages, so the round takes at most
+// (D + 15 min(D, hosts)) / 16 for D due runs — at most the calendar's runs (occupancy) and at
+// most the slabs of the buckets the window overlaps. A round edge whose free pages fall below
+// this holds before the round (Ctrl::hold) and the host grows the pool: a CoDel queue never
+// refuses a packet (codel_queue.rs:33,303-317 has no limit).
+__host__ __device__ __forceinline__ uint64_t codel_pages_bound(uint64_t due, uint64_t hosts) {
+  return (due + 15 * (due < hosts ? due : hosts) + 15) / 16;
+}
+
+// persistent rounds (k_rounds, k_rounds_x): the round buffers' sizes (RbLayout in engine.hip)
+constexpr uint32_t RB_CH = 64;  // chunk slots per buffer (persistent grids up to 4096 workgroups)
+constexpr uint32_t RB_CS_MAX = 32, RB_MS_MAX = 16, RB_OS_MAX = 16, RB_CB_MAX = (RB_CH + 1) * RB_CS_MAX;
+// the control block's host-visible copy (DevSim::ctrl_mirror)
+static_assert(sizeof(Ctrl) % 8 == 0, "the control block is copied as 8-byte words");
+constexpr uint32_t kMirrorWords = sizeof(Ctrl) / 8 + 2;  // the block, the epoch, the stale mark
+constexpr uint32_t XR_MAX = 8;  // shards of a persistent multi-shard run (one MI355X node)
+// imports of a round up to this many runs are filed by their own workgroups at the next round's
+// start (each workgroup scans them all: ~64 KB), more are shared out before a second barrier
+// (DevSim::xown; SGN_XOWN: a test hook, 0 = always shared)
+constexpr uint32_t kOwnFile = 2048;
+// inbox bins: runs per (round parity, sender, receiving host group). Config C at 8 shards sends
+// a group ~0.6 runs per sender and round, config D ~8; a fuller bin sends the rest to the slot.
+constexpr uint32_t kXBin = 32;
+// k_import's grid. few blocks: the round's received runs are a few thousand, and every block
+// counts itself in with a device atomic on one word
+constexpr uint32_t kImportBlocks = 16;
+
 }  // namespace sgn
 
 struct sgn_ctx;
@@ -807,7 +852,8 @@ int comm_round_exchange(sgn_ctx* ctx);
 int comm_bcast_blocks(sgn_ctx* ctx, void* base, size_t unit_bytes, const std::vector<uint64_t>& off);
 int comm_allreduce_minmax(sgn_ctx* ctx, uint64_t* p, size_t n_min, size_t n_max);
 int comm_allreduce_max_u32(sgn_ctx* ctx, uint32_t* p, size_t n);
-// persistent multi-shard rounds (engine.hip: the launches; comm.cpp: the IPC mapping over RCCL)
+// persistent multi-shard rounds (sim_init.cpp: the inboxes; run.cpp: the launches; comm.cpp: the
+// IPC mapping over RCCL)
 struct XLay {
   size_t hdr, cen, runs, bins, bytes;
 };
@@ -828,15 +874,55 @@ int comm_xpeer_map(sgn_ctx* ctx);       // one shard per GPU: map every peer's i
 int comm_xmove_spills(sgn_ctx* ctx, const std::vector<std::vector<EvRec>>& out,
                       std::vector<EvRec>* in);  // runs past an inbox slot, to their shards (collective)
 int comm_allreduce_max_u64(sgn_ctx* ctx, uint64_t* host_v, size_t n);  // (host values, collective)
-int inject_runs(sgn_ctx* ctx, const std::vector<EvRec>& runs);      // engine.hip: into the calendar
-// snapshot.hip's view of engine.hip: the control block to the host (overflow check), a held round
-// edge's pool growth, DevSim to the device after a pool moved, and the round kernels' shapes
-// (LDS table, persistent grid) for the calendar layout as it is now
-int ctrl_sync(sgn_ctx* ctx);
-int resolve_pools(sgn_ctx* ctx);
-int sim_upload(sgn_ctx* ctx);
-void round_kernels_resize(sgn_ctx* ctx);
 void snapshots_release(sgn_ctx* ctx);  // snapshot.hip: every snapshot the context still owns
+
+// ---- engine.hip's launch surface: the only host code in the device translation unit ----
+// The round kernels of one traffic kind, as hipLaunchKernel takes them: k_execute by [trace],
+// k_rounds by [diagnostic twin (SGN_STAMPS at sgn_sim_init: DevSim::stamps)][big-slab path], and
+// k_rounds_x. The host launches them with hipLaunchKernel and asks the same entries for their
+// occupancy and attributes (run.cpp).
+struct RoundKernels {
+  const void* execute[2];
+  const void* rounds[2][2];
+  const void* rounds_x;
+};
+const RoundKernels& round_kernels(uint32_t tkind);
+const void* import_kernel();  // k_import (a captured batch's timing nodes look for it)
+// the service kernels: the stream and the kernel's arguments, grid and block as the kernel expects
+void launch_k_import(hipStream_t st, const DevSim& S);  // (by value: captured batches hold it)
+void launch_k_inject(hipStream_t st, const DevSim* Sp, const EvRec* recs, uint32_t n);
+void launch_k_relayout(hipStream_t st, const EvRec* old_pool, uint32_t old_cap, const uint64_t* old_ext, EvRec* pool,
+                       uint32_t cap, const uint64_t* ext, EvRec* ext_pool, const uint32_t* slab_n, uint32_t* cursor,
+                       uint64_t n_slabs);
+void launch_k_relayout_ext(hipStream_t st, const uint64_t* hot, uint64_t n_hot, uint32_t max_ecap,
+                           const EvRec* old_ext_pool, const uint64_t* old_ext, uint32_t old_cap, EvRec* pool,
+                           uint32_t cap, const uint64_t* ext, EvRec* ext_pool, const uint32_t* slab_n);
+void launch_k_respill(hipStream_t st, const EvRec* spill, const uint32_t* spill_idx, uint64_t n, EvRec* pool,
+                      uint32_t cap, const uint64_t* ext, EvRec* ext_pool, uint32_t* cursor, uint32_t* lost);
+void launch_k_rng(hipStream_t st, const DevSim* Sp, const uint32_t* hosts, const uint32_t* count, const uint64_t* off,
+                  uint32_t n, uint64_t* out);
+void launch_k_rng_set(hipStream_t st, const DevSim* Sp, const uint64_t* states, uint32_t n);
+void launch_k_next_local(hipStream_t st, const DevSim* Sp, uint32_t lo, uint32_t n, uint64_t* out);
+void launch_k_next_packet(hipStream_t st, uint32_t n_buckets, const DevSim* Sp, uint32_t lo, uint32_t n, uint32_t g0,
+                          uint32_t ng, uint64_t* out);  // (one workgroup per bucket and group: n_buckets * ng)
+void launch_k_codel_law_test(hipStream_t st, uint64_t n, uint64_t* out);
+
+// ---- run.cpp: launches, the control block on the host, the run loops ----
+enum { K_EXECUTE = 0, K_IMPORT, K_NUM };  // sgn_ctx::kt rows
+inline constexpr const char* kKernelNames[K_NUM] = {"k_execute", "k_import"};
+void launch_execute(sgn_ctx* ctx);  // one round's k_execute
+void launch_import(sgn_ctx* ctx);   // k_import files the received runs and its last block advances the window
+int sync_ctrl(sgn_ctx* ctx);        // the control block to the host, overflow check
+uint32_t max_slab_capacity(sgn_ctx* ctx, const DevSim& S);
+void size_round_kernels(sgn_ctx* ctx, DevSim& S);  // the LDS table and the persistent grid for the layout as it is now
+// ---- pools.cpp: pools that grow at a held round edge ----
+int upload_sim(sgn_ctx* ctx);  // DevSim to the device after a pool moved
+int relayout_calendar(sgn_ctx* ctx);
+uint64_t codel_need_host(const sgn_ctx* ctx);
+int grow_codel(sgn_ctx* ctx, uint64_t extra);
+int grow_exchange_slot(sgn_ctx* ctx);  // larger exchange slots (runs past a slot)
+int resolve_hold(sgn_ctx* ctx);        // a held round edge's pool growth
+int inject_runs(sgn_ctx* ctx, const std::vector<EvRec>& runs);  // into the calendar
 }  // namespace sgn
 
 // Every object of libsgn is compiled against this header. A library linked from objects built
@@ -852,6 +938,10 @@ uint64_t layout_sig_api();
 uint64_t layout_sig_engine();
 uint64_t layout_sig_routes();
 uint64_t layout_sig_comm();
+uint64_t layout_sig_sim_init();
+uint64_t layout_sig_run();
+uint64_t layout_sig_pools();
+uint64_t layout_sig_interop();
 }  // namespace sgn
 
 #define SGN_HIP(ctx, call)                                   \

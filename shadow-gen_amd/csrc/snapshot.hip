@@ -303,11 +303,11 @@ int save_one(sgn_ctx* ctx, sgn_snapshot** out) {
   SGN_HIP(ctx, hipSetDevice(ctx->device));
   // CPU-held RNG states back to the device, then a resolved round edge (what sgn_run does on entry)
   if (int e = rng_release(ctx)) return e;
-  int rc = ctrl_sync(ctx);
+  int rc = sync_ctrl(ctx);
   if (rc) return rc;
   if (ctx->h_ctrl->hold || ctx->h_ctrl->spill_n) {
     ctx->ctrl_fresh = false;
-    if ((rc = resolve_pools(ctx)) || (rc = ctrl_sync(ctx))) return rc;
+    if ((rc = resolve_hold(ctx)) || (rc = sync_ctrl(ctx))) return rc;
     ctx->paused = false;
   }
   const DevSim& S = ctx->S;
@@ -520,9 +520,9 @@ int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
   S.gspec = Z.gspec;
   ctx->ext_slabs = s->ext_slabs;
   const bool relaid = codel_re || spill_re || cap_re || ext_re;
-  if (cap_re) round_kernels_resize(ctx);  // the LDS table and the persistent grid follow the slab size
+  if (cap_re) size_round_kernels(ctx, ctx->S);  // the LDS table and the persistent grid follow the slab size
   if (relaid) {
-    if (int rc = sim_upload(ctx)) {
+    if (int rc = upload_sim(ctx)) {
       ctx->failed = "sgn_snapshot_restore failed half way";
       return rc;
     }

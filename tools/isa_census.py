@@ -19,6 +19,10 @@ follows in the listing (a load waited for at once stalls the wave's only instruc
 a scalar-cache round trip), with a summary per base register:
 
     python tools/isa_census.py engine.s --smem [--kernel MANGLED] [--json]
+
+`--same A.s B.s` answers whether two builds have the same kernels (a refactor of the host code
+must not change one): every function symbol of both listings, its instruction stream compared
+with the comments stripped and the numbers of local labels blanked.
 """
 import argparse
 import collections
@@ -197,6 +201,56 @@ def smem_report(loads, srcs):
               f"{e['base']} | {e['offset']} | {e['wait'] if e['wait'] is not None else '-'} |")
 
 
+_LABEL_NO = re.compile(r"\.(LBB|Lfunc_end|Lfunc_begin|Ltmp|LJTI|LCPI)[0-9_]+")
+
+
+def functions(asm_path):
+    """{symbol: [instruction and label lines]} of a listing, in listing order: comments (from ';')
+    and directives dropped, the numbers of local labels blanked (they count functions and blocks
+    of the whole file, so they shift when another function is added or the order changes)."""
+    out = {}
+    cur = None
+    is_fn = set()
+    with open(asm_path, errors="replace") as f:
+        for ln in f:
+            m = re.match(r"^\s*\.type\s+([^,\s]+),@function", ln)
+            if m:
+                is_fn.add(m.group(1))
+                continue
+            m = re.match(r"^([A-Za-z_][\w$.]*):", ln)
+            if m and cur is None and m.group(1) in is_fn:
+                cur = out.setdefault(m.group(1), [])
+                continue
+            if ln.startswith(".Lfunc_end"):
+                cur = None
+                continue
+            if cur is None:
+                continue
+            s = _LABEL_NO.sub(lambda k: "." + k.group(1) + "_", ln.split(";")[0]).strip()
+            if s and (not s.startswith(".") or s.startswith(".L")):
+                cur.append(s)
+    return out
+
+
+def same(a_path, b_path):
+    """Compare two listings function by function; prints one line each and returns 0 when both
+    hold the same symbols with identical instruction streams."""
+    a, b = functions(a_path), functions(b_path)
+    bad = 0
+    for sym in sorted(set(a) | set(b)):
+        if sym not in a or sym not in b:
+            print(f"ONLY IN {'A' if sym in a else 'B'}  {sym}")
+            bad += 1
+        elif a[sym] != b[sym]:
+            first = next((i for i, (x, y) in enumerate(zip(a[sym], b[sym])) if x != y), min(len(a[sym]), len(b[sym])))
+            print(f"DIFFERENT  {sym}: {len(a[sym])} vs {len(b[sym])} lines, first difference at line {first}")
+            bad += 1
+        else:
+            print(f"same  {len(a[sym]):6d} lines  {sym}")
+    print(f"{len(a)} functions in A, {len(b)} in B, {bad} differ")
+    return 1 if bad else 0
+
+
 def source_line(path_by_name, key):
     p = path_by_name.get(key[0])
     if not p or key[1] == 0:
@@ -217,7 +271,11 @@ def main():
     ap.add_argument("--per-copy", default="", help="comma-separated FILE:LINE list: instructions per inlined copy")
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--smem", action="store_true", help="list the kernel's scalar loads instead of the census")
+    ap.add_argument("--same", nargs=2, metavar=("A.s", "B.s"),
+                    help="compare two listings function by function (exit status 1 when they differ)")
     a = ap.parse_args()
+    if a.same:
+        return same(*a.same)
     if a.compile:
         compile_asm(a.compile, a.o)
         return 0
