@@ -340,6 +340,64 @@ int sgn_shards_snapshot_save(sgn_ctx* const* ctxs, uint32_t n, sgn_snapshot** ou
  * the last sgn_sim_init. */
 int sgn_shards_snapshot_restore(sgn_ctx* const* ctxs, uint32_t n, sgn_snapshot* const* snaps /* [n] */);
 
+/* ---- snapshot files: a snapshot out of its context and process, and back into a fresh one ----
+ * The reference has no checkpoint (a restart re-runs from t = 0). A snapshot's state is
+ * pointer-free, so a file is a matter of format and validation: a header (what wrote it, which
+ * simulation, the round edge, the pool layout), a table {id, bytes, digest} of sections, the
+ * sections (every device buffer of the snapshot, the packed calendar, the host-side vectors, the
+ * trace records up to the save), and a trailer digest over header and table. Little-endian, every
+ * section padded to 16 bytes. A file belongs to the library build that wrote it — it is not an
+ * interchange format — and to one simulation: the header carries an IDENTITY digest of the route
+ * table, every host's constants (address, node, bandwidths, seed), the sgn_sim_config and
+ * sgn_traffic fields (server list included), the shard rank, count and owned range, and the
+ * calendar's shape; the same calls in another process give the same identity. */
+#define SGN_EFILE (-74) /* a snapshot file is truncated, corrupt, or a stream callback failed */
+
+/* Stream callbacks: called in order, never asked to seek. Return 0 when all len bytes were
+ * written / filled; anything else ends the call with SGN_EFILE. */
+typedef int (*sgn_write_fn)(void* user, const void* data, size_t len);
+typedef int (*sgn_read_fn)(void* user, void* data, size_t len);
+
+/* Writes snap (owned by ctx, of the current sgn_sim_init: else the errors of sgn_snapshot_restore)
+ * in one forward pass: header and table, the sections, the trailer. Neither the simulation nor the
+ * snapshot changes. Device sections are digested on the device before they leave and stream
+ * through two pinned staging chunks, so host memory stays bounded whatever the snapshot's size.
+ * Trace records [0, min(trace count at the save, capacity)) are taken from the context's trace
+ * buffer (append-only, and the engine is deterministic: they are still there). bytes (may be
+ * NULL): the file's length. */
+int sgn_snapshot_export(sgn_ctx* ctx, const sgn_snapshot* snap, sgn_write_fn write, void* user, uint64_t* bytes);
+
+/* Builds a new snapshot owned by ctx from a stream, as if sgn_snapshot_save had just taken it here
+ * — and does nothing else: the simulation is untouched until sgn_snapshot_restore (or
+ * sgn_shards_snapshot_restore: every shard imports its own file, no collective needed) is called
+ * with it. Needs a simulation made by the same calls as the exporter's (SGN_ESTATE without one).
+ * All or nothing: on any failure every buffer is freed and *out is NULL.
+ * Errors: SGN_EINVAL when a header field differs from this library or this simulation (the
+ * message names the field; another identity is one of them); SGN_EFILE for a truncated stream, a
+ * section whose size does not follow from the simulation and the header, a section or trailer
+ * digest that does not match (sections are digested again on the device after the upload; the
+ * message names the section), or slab fills that disagree with the packed calendar's run count;
+ * SGN_ESTATE for a file with trace records into a context without a trace buffer that holds them
+ * (or the reverse). The imported snapshot carries its trace records and a restore writes them
+ * back; sgn_snapshot_info_get reports the saved round, window, sizes and runs, save_ms = pack_ms
+ * = 0. */
+int sgn_snapshot_import(sgn_ctx* ctx, sgn_read_fn read, void* user, sgn_snapshot** out);
+
+/* The same through a file: export writes path + ".tmp" and renames it on success (a failure
+ * removes the temporary file and leaves path alone); import reads path (SGN_ENOENT: cannot open). */
+int sgn_snapshot_export_file(sgn_ctx* ctx, const sgn_snapshot* snap, const char* path, uint64_t* bytes);
+int sgn_snapshot_import_file(sgn_ctx* ctx, const char* path, sgn_snapshot** out);
+
+/* A file's header: no device call, no context. SGN_ENOENT when path cannot be opened, SGN_EFILE
+ * when it is shorter than its header says, has another magic, or its trailer digest fails. */
+typedef struct sgn_snapshot_file_info {
+  uint64_t format, abi, layout_sig, identity; /* what wrote it, and which simulation */
+  uint64_t rounds, window_start, window_end;  /* the round edge */
+  uint64_t file_bytes, n_sections, calendar_runs, trace_records;
+  uint32_t shard_rank, shard_count;
+} sgn_snapshot_file_info;
+int sgn_snapshot_file_info_get(const char* path, sgn_snapshot_file_info* out);
+
 /* Whole-simulation counters (summed over owned hosts). */
 typedef struct sgn_stats {
   uint64_t rounds;
@@ -718,6 +776,25 @@ int64_t sgn_trace_pcap(const sgn_trace_rec* recs, uint64_t n, uint32_t host, con
 /* Device CoDel control-law increments round(1e8 / sqrt(count)) for count in [0, n)
  * (router/codel_queue.rs:285-298), for checking device f64 rounding against the host. */
 int sgn_selftest_codel_law(sgn_ctx* ctx, uint64_t n, uint64_t* out);
+
+/* The section digest of snapshot files, for len % 4 == 0: with w_j the little-endian u64 at byte
+ * 8j (a 4-byte tail zero-extended), D = mix64(len ^ SGN_DIGEST_SEED) + sum_j mix64(w_j ^
+ * (0x9e3779b97f4a7c15 * (j + 1))) mod 2^64 (sgn_mix64, sgn_workload.h): position-keyed terms under
+ * a commutative sum, so any order of evaluation gives the same value. sgn_digest_bytes is the host
+ * form (0 for len % 4 != 0 or a null p with len > 0); sgn_selftest_digest runs the device kernel
+ * on a copy of host_bytes. */
+uint64_t sgn_digest_bytes(const void* p, size_t len);
+int sgn_selftest_digest(sgn_ctx* ctx, const void* host_bytes, size_t len, uint64_t* out);
+
+/* What the context's last sgn_snapshot_export / _import spent (measurements; tools/snapshot_timing.py). */
+typedef struct sgn_snapshot_file_timing {
+  double total_ms;       /* wall time of the call */
+  double stream_ms;      /* ... of which the payloads: device <-> pinned chunk <-> callback */
+  double digest_ms;      /* HIP-event time of the one digest launch over the device sections */
+  uint64_t device_bytes; /* bytes that launch read */
+  uint64_t file_bytes;
+} sgn_snapshot_file_timing;
+int sgn_snapshot_file_timing_get(sgn_ctx* ctx, sgn_snapshot_file_timing* out);
 
 /* Diagnostics of the last execute launch, SGN_STAMP_WORDS u64 per wave: {shader cycles,
  * events handled, max events of one host, hosts with events, then (diagnostic build

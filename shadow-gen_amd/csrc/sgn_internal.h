@@ -824,6 +824,14 @@ struct sgn_ctx {
   uint64_t sim_gen = 0;
   bool paused = false;  // the last held round edge carried HOLD_PAUSE (sgn_run_until and
                         // sgn_shards_run_until stop on it)
+  // snapshot files (snapshot_file.hip): the arguments of the last sgn_sim_init (server_hosts is
+  // null here: the list is DevSim::servers), and the identity digest made from them and from the
+  // routes and hosts at the first export or import of this simulation (identity_gen == sim_gen)
+  sgn_sim_config sim_cfg{};
+  sgn_traffic sim_tr{};
+  uint64_t identity = 0, identity_gen = 0;
+  void* file_stage[2] = {nullptr, nullptr};  // pinned staging chunks of the file stream
+  sgn_snapshot_file_timing file_timing{};    // of the last export or import
 
   ~sgn_ctx();
 };
@@ -942,6 +950,7 @@ uint64_t layout_sig_sim_init();
 uint64_t layout_sig_run();
 uint64_t layout_sig_pools();
 uint64_t layout_sig_interop();
+uint64_t layout_sig_snapshot_file();
 }  // namespace sgn
 
 #define SGN_HIP(ctx, call)                                   \

@@ -654,6 +654,9 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
   ctx->S = S;
   ctx->sim_ready = true;
   ctx->sim_gen++;  // (snapshots of the simulation before this one are refused from here)
+  ctx->sim_cfg = *cfg;  // (a snapshot file's identity digest is made from these, when first asked for)
+  ctx->sim_tr = *tr;
+  ctx->sim_tr.server_hosts = nullptr;
   ctx->paused = false;
   ctx->rounds_enqueued = 0;
   for (int i = 0; i < K_NUM; i++) ctx->kt[i] = {kKernelNames[i], 0, 0.0, 0};

@@ -10,7 +10,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "sgn_internal.h"
+#include "snapshot_priv.h"
 
 using namespace sgn;
 
@@ -175,34 +175,6 @@ __global__ __launch_bounds__(kWaveSlabs * kCopyWaves) void k_snap_copy(
 }  // namespace
 
 // ---- host side ------------------------------------------------------------------------------
-struct sgn_snapshot {
-  sgn_ctx* ctx = nullptr;
-  uint64_t gen = 0;
-  DevSim S{};   // the layout at save: CAP, cq_pages, spill_cap, ext_total, gspec (its pointers are
-                // the buffers of that time and are never followed)
-  Ctrl ctrl{};  // the control block at save
-  struct Buf {
-    void* d = nullptr;
-    size_t bytes = 0;
-  };
-  std::vector<Buf> fixed;                         // state_buffers() order
-  Buf codel, cq_next, cq_free, spill, spill_idx;  // the pools that grow
-  Buf drain;                                      // undrained records [0, drain_n)
-  Buf packed;                                     // the calendar's runs
-  uint64_t runs = 0;
-  // host-side simulation state
-  uint64_t rounds_enqueued = 0;
-  std::vector<uint64_t> handles;
-  std::vector<uint32_t> submit_seq;
-  std::vector<sgn_drain_rec> drain_held;
-  std::vector<uint64_t> h_ext;
-  uint64_t codel_grows = 0, cal_grows = 0, cal_spill_runs = 0, ext_slabs = 0, spill_grows = 0, rounds_held = 0,
-           codel_allocs_before = 0;
-  sgn_snapshot_info info{};
-};
-
-namespace {
-
 using Buf = sgn_snapshot::Buf;
 
 // The mutable buffers of DevSim that never move or change size after sgn_sim_init, in a fixed
@@ -211,7 +183,7 @@ using Buf = sgn_snapshot::Buf;
 // state; the round buffers (rb_min, rb_keep, rb_cnt, rb_occ, fin_*) are idle at a round edge —
 // the per-round finalize exchanges them back to their reset values and a persistent launch resets
 // them itself before its census; rb_free is three words of that kind, saved anyway.
-std::vector<std::pair<void*, size_t>> state_buffers(const DevSim& S) {
+std::vector<std::pair<void*, size_t>> sgn::state_buffers(const DevSim& S) {
   const size_t nH = S.nH, n_slabs = (size_t)(S.NB + 1) * S.G;
   std::vector<std::pair<void*, size_t>> v;
   v.push_back({(void*)S.hrec, nH * sizeof(HostRec)});
@@ -229,22 +201,41 @@ std::vector<std::pair<void*, size_t>> state_buffers(const DevSim& S) {
   v.push_back({(void*)S.w_cnt, (size_t)W_N * S.G * 8});
   return v;
 }
+const char* const sgn::kStateBufferNames[] = {"hrec",     "htile",     "n_cnt",  "maxq",        "nextloc",    "npeer", "rb_free",
+                                              "fifo",     "fifo_addr", "slab_n", "bucket_slab", "bucket_min", "w_cnt"};
 
-bool buf_alloc(Buf* b, size_t bytes) {
+bool sgn::snap_buf_alloc(Buf* b, size_t bytes) {
   b->d = nullptr;
   b->bytes = bytes;
   return bytes == 0 || hipMalloc(&b->d, bytes) == hipSuccess;
 }
-void buf_free(Buf* b) {
-  if (b->d) (void)hipFree(b->d);
-  b->d = nullptr;
-  b->bytes = 0;
-}
-void snap_release(sgn_snapshot* s) {
+void sgn::snap_release(sgn_snapshot* s) {
+  auto buf_free = [](Buf* b) {
+    if (b->d) (void)hipFree(b->d);
+    b->d = nullptr;
+    b->bytes = 0;
+  };
   for (Buf& b : s->fixed) buf_free(&b);
-  for (Buf* b : {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain, &s->packed}) buf_free(b);
+  for (Buf* b : {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain, &s->packed, &s->trace})
+    buf_free(b);
   delete s;
 }
+void sgn::snap_fill_info(sgn_snapshot* s, uint64_t n_slabs) {
+  sgn_snapshot_info& in = s->info;
+  in.rounds = s->ctrl.rounds;
+  in.window_start = s->ctrl.ws;
+  in.window_end = s->ctrl.we;
+  in.device_bytes = s->packed.bytes + s->trace.bytes;
+  for (const Buf& b : s->fixed) in.device_bytes += b.bytes;
+  for (const Buf* b : {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain}) in.device_bytes += b->bytes;
+  in.host_bytes = sizeof(sgn_snapshot) + s->fixed.size() * sizeof(Buf) + s->handles.size() * 8 + s->submit_seq.size() * 4 +
+                  s->drain_held.size() * sizeof(sgn_drain_rec) + s->h_ext.size() * 8;
+  in.calendar_runs = s->runs;
+  in.calendar_bytes = s->runs * sizeof(EvRec);
+  in.calendar_pool_bytes = (n_slabs * s->S.CAP + s->S.ext_total) * sizeof(EvRec);
+}
+namespace {
+inline bool buf_alloc(Buf* b, size_t bytes) { return snap_buf_alloc(b, bytes); }
 
 // the scan's scratch: off (n_slabs + 1 words, the last the total) and the tile sums
 struct Scan {
@@ -400,17 +391,7 @@ int save_one(sgn_ctx* ctx, sgn_snapshot** out) {
   s->rounds_held = ctx->rounds_held;
   s->codel_allocs_before = ctx->codel_allocs_before;
   sgn_snapshot_info& in = s->info;
-  in.rounds = c.rounds;
-  in.window_start = c.ws;
-  in.window_end = c.we;
-  in.device_bytes = s->packed.bytes;
-  for (const Buf& b : s->fixed) in.device_bytes += b.bytes;
-  for (const Buf* b : {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain}) in.device_bytes += b->bytes;
-  in.host_bytes = sizeof(sgn_snapshot) + s->fixed.size() * sizeof(Buf) + s->handles.size() * 8 + s->submit_seq.size() * 4 +
-                  s->drain_held.size() * sizeof(sgn_drain_rec) + s->h_ext.size() * 8;
-  in.calendar_runs = total;
-  in.calendar_bytes = total * sizeof(EvRec);
-  in.calendar_pool_bytes = (n_slabs * S.CAP + S.ext_total) * sizeof(EvRec);
+  snap_fill_info(s, n_slabs);
   in.save_ms = (double)ms_scan + (double)ms_pack + (double)ms_rest;
   in.pack_ms = (double)ms_scan + (double)ms_pack;
   ctx->snapshots.push_back(s);
@@ -418,8 +399,10 @@ int save_one(sgn_ctx* ctx, sgn_snapshot** out) {
   return 0;
 }
 
-// what a restore checks before it touches anything (what: the entry point's name)
-int restore_check(sgn_ctx* ctx, const sgn_snapshot* snap, const char* what, sgn_snapshot** s_out) {
+}  // namespace
+
+// what a restore (and an export) checks before it touches anything (what: the entry point's name)
+int sgn::snap_check(sgn_ctx* ctx, const sgn_snapshot* snap, const char* what, sgn_snapshot** s_out) {
   const std::string w(what);
   sgn_snapshot* s = owned(ctx, snap);
   if (!s) return set_error(ctx, SGN_EINVAL, w + ": not a snapshot of this context");
@@ -429,6 +412,22 @@ int restore_check(sgn_ctx* ctx, const sgn_snapshot* snap, const char* what, sgn_
   if (!ctx->failed.empty()) return set_error(ctx, SGN_ESTATE, "simulation unusable: " + ctx->failed);
   *s_out = s;
   return 0;
+}
+
+int sgn::snap_scan_total(sgn_ctx* ctx, const uint32_t* slab_n, const uint64_t* ext, uint32_t cap, uint64_t n_slabs,
+                         uint64_t* total) {
+  Scan sc;
+  if (!sc.alloc(n_slabs)) return set_error(ctx, SGN_ENOMEM, "device allocation failed (calendar scan)");
+  launch_scan(ctx->stream, sc, slab_n, ext, cap, n_slabs);
+  if (hipMemcpyAsync(total, sc.off + n_slabs, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return set_error(ctx, SGN_EDEVICE, "snapshot: the calendar scan failed");
+  return 0;
+}
+
+namespace {
+inline int restore_check(sgn_ctx* ctx, const sgn_snapshot* snap, const char* what, sgn_snapshot** s_out) {
+  return snap_check(ctx, snap, what, s_out);
 }
 
 // One context back to its snapshot s (checked by restore_check). shard: a shard of a sharded run
@@ -539,6 +538,9 @@ int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
   for (size_t k = 0; ok && k < dst.size(); k++) ok = dst[k].second == s->fixed[k].bytes && d2d(dst[k].first, s->fixed[k]);
   ok = ok && d2d((void*)S.codel, s->codel) && d2d((void*)S.cq_next, s->cq_next) && d2d((void*)S.cq_free, s->cq_free) &&
        d2d((void*)S.spill, s->spill) && d2d((void*)S.spill_idx, s->spill_idx) && d2d((void*)S.drain, s->drain);
+  // an imported snapshot brings the trace records up to its save (import checked that they fit);
+  // one saved here has none: this context's trace buffer still holds them
+  if (s->trace.bytes) ok = ok && S.trace && s->trace.bytes <= S.trace_cap * sizeof(sgn_trace_rec) && d2d((void*)S.trace, s->trace);
   if (ok && s->runs) {
     // (the fills just restored, in stream order; the same scan as at save: the same offsets)
     launch_scan(st, sc, (const uint32_t*)S.slab_n, (const uint64_t*)S.ext, S.CAP, n_slabs);

@@ -191,6 +191,22 @@ class SnapshotInfo(C.Structure):
         "calendar_bytes", "calendar_pool_bytes")] + [("save_ms", C.c_double), ("pack_ms", C.c_double)]
 
 
+class SnapshotFileInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "format", "abi", "layout_sig", "identity", "rounds", "window_start", "window_end", "file_bytes",
+        "n_sections", "calendar_runs", "trace_records")] + [("shard_rank", C.c_uint32), ("shard_count", C.c_uint32)]
+
+
+class SnapshotFileTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_double), ("stream_ms", C.c_double), ("digest_ms", C.c_double),
+                ("device_bytes", C.c_uint64), ("file_bytes", C.c_uint64)]
+
+
+EFILE = -74
+WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)  # sgn_write_fn
+READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)   # sgn_read_fn
+
+
 class KernelTimes(C.Structure):
     _fields_ = [("launches", C.c_uint64 * 16), ("ms", C.c_double * 16),
                 ("name", C.c_char_p * 16), ("n_kernels", C.c_uint32),
@@ -299,6 +315,14 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         "sgn_shards_run_until": (C.c_int, [C.POINTER(vp), C.c_uint32, C.c_uint64, u64p]),
         "sgn_shards_snapshot_save": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
         "sgn_shards_snapshot_restore": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
+        "sgn_snapshot_export": (C.c_int, [vp, vp, WRITE_FN, vp, u64p]),
+        "sgn_snapshot_import": (C.c_int, [vp, READ_FN, vp, C.POINTER(vp)]),
+        "sgn_snapshot_export_file": (C.c_int, [vp, vp, C.c_char_p, u64p]),
+        "sgn_snapshot_import_file": (C.c_int, [vp, C.c_char_p, C.POINTER(vp)]),
+        "sgn_snapshot_file_info_get": (C.c_int, [C.c_char_p, C.POINTER(SnapshotFileInfo)]),
+        "sgn_snapshot_file_timing_get": (C.c_int, [vp, C.POINTER(SnapshotFileTiming)]),
+        "sgn_digest_bytes": (C.c_uint64, [vp, C.c_size_t]),
+        "sgn_selftest_digest": (C.c_int, [vp, vp, C.c_size_t, u64p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -495,6 +519,59 @@ class Context:
             raise SgnError(rc, "sgn_snapshot_info_get: null argument")
         return {n: getattr(i, n) for n, _ in i._fields_}
 
+    # ---- snapshot files: a snapshot out of this context and process, and into a fresh one ----
+    def snapshot_export(self, snap, path):
+        """Writes snap to path (through path.tmp and a rename); returns the file's length."""
+        n = C.c_uint64()
+        self.check(self.L.sgn_snapshot_export_file(self.h, snap, os.fsencode(path), C.byref(n)))
+        return n.value
+
+    def snapshot_import(self, path):
+        """A new snapshot of this context from a file written by a simulation made by the same
+        calls; nothing else changes until snapshot_restore (or shards_snapshot_restore)."""
+        s = C.c_void_p()
+        self.check(self.L.sgn_snapshot_import_file(self.h, os.fsencode(path), C.byref(s)))
+        return s
+
+    def snapshot_export_stream(self, snap, write):
+        """The stream form: write(bytes) is called in file order; a false return or an exception
+        ends the export with EFILE. Returns the stream's length."""
+        def cb(_user, data, n):
+            try:
+                return 0 if write(C.string_at(data, n)) is not False else 1
+            except Exception:  # noqa: BLE001 (nothing may unwind across the C ABI)
+                return 1
+        n = C.c_uint64()
+        self.check(self.L.sgn_snapshot_export(self.h, snap, WRITE_FN(cb), None, C.byref(n)))
+        return n.value
+
+    def snapshot_import_stream(self, read):
+        """The stream form: read(n) returns exactly n bytes (fewer: EFILE)."""
+        def cb(_user, data, n):
+            try:
+                b = read(n)
+            except Exception:  # noqa: BLE001
+                return 1
+            if b is None or len(b) != n:
+                return 1
+            C.memmove(data, b, n)
+            return 0
+        s = C.c_void_p()
+        self.check(self.L.sgn_snapshot_import(self.h, READ_FN(cb), None, C.byref(s)))
+        return s
+
+    def snapshot_file_timing(self):
+        t = SnapshotFileTiming()
+        self.check(self.L.sgn_snapshot_file_timing_get(self.h, C.byref(t)))
+        return {n: getattr(t, n) for n, _ in t._fields_}
+
+    def selftest_digest(self, buf):
+        """The section digest of buf (bytes-like, a multiple of 4 bytes) by the device kernel."""
+        a = np.frombuffer(bytes(buf), dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+        out = C.c_uint64()
+        self.check(self.L.sgn_selftest_digest(self.h, a.ctypes.data if a.size else None, a.size, C.byref(out)))
+        return out.value
+
     def stats(self):
         s = Stats()
         self.check(self.L.sgn_stats_get(self.h, C.byref(s)))
@@ -635,6 +712,47 @@ def shards_snapshot_save(shards):
 def shards_snapshot_restore(shards, snaps):
     arr = (C.c_void_p * len(snaps))(*[s.value if isinstance(s, C.c_void_p) else s for s in snaps])
     _shards_call(shards, "sgn_shards_snapshot_restore", arr)
+
+
+def snapshot_file_info(path, lib=None):
+    """A snapshot file's header (no device, no context): SgnError with rc -2 when the path cannot
+    be opened, EFILE when the file is truncated, has another magic or fails its trailer digest."""
+    L = lib or load()
+    i = SnapshotFileInfo()
+    rc = L.sgn_snapshot_file_info_get(os.fsencode(path), C.byref(i))
+    if rc != 0:
+        raise SgnError(rc, f"sgn_snapshot_file_info_get: {path}")
+    return {n: int(getattr(i, n)) for n, _ in i._fields_}
+
+
+SNAPSHOT_HEADER_BYTES = 288  # snapshot_file.hip FileHeader: the magic and 35 little-endian u64
+SNAPSHOT_SECTION_NAMES = ("ctrl", "hrec", "htile", "n_cnt", "maxq", "nextloc", "npeer", "rb_free", "fifo",
+                          "fifo_addr", "slab_n", "bucket_slab", "bucket_min", "w_cnt", "codel", "cq_next",
+                          "cq_free", "spill", "spill_idx", "drain", "calendar", "handles", "submit_seq",
+                          "drain_held", "h_ext", "trace")
+
+
+def snapshot_file_sections(path):
+    """The section table of a snapshot file as [{name, id, bytes, digest, offset}] (offset: of the
+    payload in the file; payloads are padded to 16 bytes), read as DESIGN.md lays the file out."""
+    n = snapshot_file_info(path)["n_sections"]
+    with open(path, "rb") as f:
+        f.seek(SNAPSHOT_HEADER_BYTES)
+        tab = np.frombuffer(f.read(24 * n), dtype="<u8").reshape(n, 3)
+    off = SNAPSHOT_HEADER_BYTES + 24 * n
+    out = []
+    for i, (sid, nbytes, dig) in enumerate(tab.tolist()):
+        name = SNAPSHOT_SECTION_NAMES[i] if i < len(SNAPSHOT_SECTION_NAMES) else str(sid)
+        out.append({"name": name, "id": sid, "bytes": nbytes, "digest": dig, "offset": off})
+        off += (nbytes + 15) // 16 * 16
+    return out
+
+
+def digest_bytes(buf, lib=None):
+    """The section digest of snapshot files over buf (bytes-like, a multiple of 4 bytes), host form."""
+    L = lib or load()
+    a = np.ascontiguousarray(buf).view(np.uint8).reshape(-1) if isinstance(buf, np.ndarray) else np.frombuffer(bytes(buf), dtype=np.uint8)
+    return int(L.sgn_digest_bytes(a.ctypes.data if a.size else None, a.size))
 
 
 # ------------------------------------------------------------------------------------

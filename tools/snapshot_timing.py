@@ -6,10 +6,16 @@ calendar, the time a raw device-to-device copy of the unpacked calendar takes in
 was before snapshots: sgn_sim_init + sgn_run to the same round.
 
 usage: python tools/snapshot_timing.py [--workload C D] [--rounds 1500] [--shards N] [--out FILE]
+                                       [--export DIR]
 The save is taken after bench.py's warm-up + steps worth of rounds (5 + 10 steps of 100).
 --shards N: the same hosts as N shards of one local group on this GPU, saved and restored with
 the collective calls (sgn_shards_snapshot_*): per-shard save times (their maximum and their sum:
-the shards save one after the other) and the wall time of the group's save and restore."""
+the shards save one after the other) and the wall time of the group's save and restore.
+--export DIR: snapshot files instead. The snapshot goes to DIR/<workload>.snap (the second export is
+timed: the staging chunks are pinned by then) and into a FRESH context of the same simulation
+(import, then restore): wall times, the digest kernel's time and rate over the device sections at
+export and at import, and in the same process a device-to-device copy and the pinned-host
+transfers of the same bytes. The lines are appended to profiles/snapshot_timing.jsonl."""
 import argparse
 import ctypes as C
 import json
@@ -96,6 +102,88 @@ def measure(name, rounds):
     }
 
 
+def pinned_copy_ms(nbytes, to_host):
+    """nbytes between the device and pinned host memory, in pieces of a 256 MiB pinned buffer (the
+    second pass is timed)."""
+    piece = min(nbytes, 256 << 20)
+    dev = torch.empty(piece, dtype=torch.uint8, device="cuda").zero_()
+    host = torch.empty(piece, dtype=torch.uint8).pin_memory()
+    ms = 0.0
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        left = nbytes
+        while left > 0:
+            k = min(left, piece)
+            if to_host:
+                host[:k].copy_(dev[:k], non_blocking=True)
+            else:
+                dev[:k].copy_(host[:k], non_blocking=True)
+            left -= k
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+    del dev, host
+    torch.cuda.empty_cache()
+    return ms
+
+
+def measure_export(name, rounds, out_dir):
+    g, used, hosts, cfg, tr = workload(name, rounds)
+
+    def fresh():
+        c = sgn.Context(device=0)
+        c.routes_build(g, used)
+        c.hosts_set(hosts)
+        c.sim_init(cfg, tr)
+        return c
+
+    c = fresh()
+    done = c.run(rounds)
+    w = c.window()
+    snap = c.snapshot_save()
+    info = c.snapshot_info(snap)
+    path = pathlib.Path(out_dir) / f"{name}.snap"
+    c.snapshot_export(snap, path)  # (the first export pins the staging chunks)
+    path.unlink()  # (or the timed export's rename pays for freeing this file's pages)
+    t0 = time.perf_counter()
+    nbytes = c.snapshot_export(snap, path)
+    export_ms = (time.perf_counter() - t0) * 1e3
+    te = c.snapshot_file_timing()
+    c.close()
+    c = fresh()  # never ran a round: its pools stand at their initial sizes
+    s0 = c.snapshot_import(path)
+    c.snapshot_free(s0)
+    t0 = time.perf_counter()
+    s1 = c.snapshot_import(path)
+    import_ms = (time.perf_counter() - t0) * 1e3
+    ti = c.snapshot_file_timing()
+    t0 = time.perf_counter()
+    c.snapshot_restore(s1)
+    restore_ms = (time.perf_counter() - t0) * 1e3
+    assert c.window() == w and c.stats()["rounds"] == done
+    c.close()
+    path.unlink()
+    dev = te["device_bytes"]
+    d2d_ms = raw_copy_ms(dev)
+    d2h_ms, h2d_ms = pinned_copy_ms(dev, True), pinned_copy_ms(dev, False)
+    rate = lambda b, ms: round(b / max(ms, 1e-6) / 1e6, 2)  # noqa: E731 (GB/s)
+    return {
+        "tool": "snapshot_timing_export", "build_id": sgn.build_id(), "workload": name, "hosts": hosts.n,
+        "rounds_at_save": done, "file_bytes": nbytes, "device_section_bytes": dev,
+        "snapshot_device_bytes": info["device_bytes"], "calendar_runs": info["calendar_runs"],
+        "export_wall_ms": round(export_ms, 3), "export_call_ms": round(te["total_ms"], 3), "export_stream_ms": round(te["stream_ms"], 3),
+        "export_digest_ms": round(te["digest_ms"], 4), "export_digest_gb_per_s": rate(dev, te["digest_ms"]),
+        "import_wall_ms": round(import_ms, 3), "import_call_ms": round(ti["total_ms"], 3), "import_stream_ms": round(ti["stream_ms"], 3),
+        "import_digest_ms": round(ti["digest_ms"], 4), "import_digest_gb_per_s": rate(ti["device_bytes"], ti["digest_ms"]),
+        "restore_wall_ms": round(restore_ms, 3),
+        "d2d_copy_ms": round(d2d_ms, 4), "d2d_copy_gb_per_s": rate(dev, d2d_ms),
+        "pinned_d2h_ms": round(d2h_ms, 3), "pinned_d2h_gb_per_s": rate(dev, d2h_ms),
+        "pinned_h2d_ms": round(h2d_ms, 3), "pinned_h2d_gb_per_s": rate(dev, h2d_ms),
+        "export_digest_share": round(te["digest_ms"] / max(export_ms, 1e-6), 5),
+        "import_digest_share": round(ti["digest_ms"] / max(import_ms, 1e-6), 5),
+    }
+
+
 def measure_group(name, rounds, k):
     g, used, hosts, cfg, tr = workload(name, rounds)
     cfg = type(cfg).from_buffer_copy(cfg)
@@ -152,8 +240,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=1500)
     ap.add_argument("--out", default=None)
     ap.add_argument("--shards", type=int, default=1)
+    ap.add_argument("--export", metavar="DIR", default=None)
     args = ap.parse_args()
-    if args.shards > 1:
+    if args.export:
+        lines = [json.dumps(measure_export(w, args.rounds, args.export)) for w in args.workload]
+        with open(ROOT / "profiles" / "snapshot_timing.jsonl", "a") as f:
+            f.write("\n".join(lines) + "\n")
+    elif args.shards > 1:
         lines = [json.dumps(measure_group(w, args.rounds, args.shards)) for w in args.workload]
     else:
         lines = [json.dumps(measure(w, args.rounds)) for w in args.workload]
