@@ -1563,10 +1563,12 @@ struct HostExec {
   // digest takes runs of equal outcomes. Sent packets take consecutive source event ids and
   // share one delivery time, so their events are reserved with one atomic and written as
   // one contiguous run.
-  // pop: (trace) each packet was just popped from the interface (an IF_POP record precedes its
-  // SEND record, as NetworkInterface::pop precedes send_packet)
+  // pop: (trace) the index of the first packet that was just popped from the interface (an
+  // IF_POP record precedes its SEND record, as NetworkInterface::pop precedes send_packet);
+  // the packets before it were popped earlier (a cached packet), NO_POP: none was
+  static constexpr uint32_t NO_POP = ~0u;
   __device__ __forceinline__ void send_batch(uint32_t dst, uint32_t payload, uint32_t tag, uint32_t n,
-                                             bool pop = false) {
+                                             uint32_t pop = NO_POP) {
     DGT_BEGIN(t0);
     send_batch_(dst, payload, tag, n, pop);
     DGT_END(DGT_SEND, t0);
@@ -1590,16 +1592,18 @@ struct HostExec {
     trace(SGN_TRACE_IF_POP, dst, 0, now, (uint64_t)payload | ((uint64_t)tag << 32),
           dst == NO_HOST ? SK(fifo_addr)[fq_slot(0) - SK(fifo)] : 0);
   }
-  __device__ __forceinline__ void send_batch_(uint32_t dst, uint32_t payload, uint32_t tag, uint32_t n, bool pop) {
+  __device__ __forceinline__ void send_batch_(uint32_t dst, uint32_t payload, uint32_t tag, uint32_t n, uint32_t pop) {
     if (n == 0 || now >= SK(end_time)) return;
     DG(DG_BATCH);
     const bool boot = now < SK(boot_end);
+    // (only the TGEN kernels send a cached packet with popped ones: elsewhere pop is 0 or NO_POP)
+    const auto popped = [&](uint32_t j) { return kApp == SGN_TRAFFIC_TGEN ? j >= pop : pop == 0; };
     if (dst == NO_HOST) {  // resolve_ip_to_host_id failed: InetDropped (worker.rs:347-357)
       cnt_add(&R->n_unknown, n);
       dr_add_same<0>(now, 0xFFFFFFFFULL | (2ULL << 32), 0, n);
       if (tr())
         for (uint32_t j = 0; j < n; j++) {
-          if (pop) trace_pop(NO_HOST, payload, tag);
+          if (popped(j)) trace_pop(NO_HOST, payload, tag);
           trace(SGN_TRACE_SEND, 0xFFFFFFFFu, 2, now, 0, 0);
         }
       if (external())
@@ -1657,7 +1661,7 @@ struct HostExec {
 #endif
     if (tr() || external()) {  // per-packet records
       for (uint32_t j = 0; j < n; j++) {
-        if (tr() && pop) trace_pop(dst, payload, tag);
+        if (tr() && popped(j)) trace_pop(dst, payload, tag);
         const uint64_t x = rng_next() >> 11;
         if (tr()) R->rng_pos++;
         if (can_drop && x >= T) {
@@ -1875,6 +1879,16 @@ struct HostExec {
   // `now` does not move and none of its other events run until the queue is empty or the
   // bucket blocks), so lanes forwarding long trains send them side by side instead of one
   // after another (a train's per-packet loss draws are the serial part of a round).
+  // TGEN: a cached packet that the head entry's run continues (a train the bucket blocked
+  // in mid-file: the same peer, tag and size) goes out with that run in one step — one
+  // removal from the bucket for both (tb_take's n calls at one `now`), one send_batch: the
+  // same draws in the same order, one event run at the receiver instead of two that it
+  // would merge again.
+  __device__ __forceinline__ bool merges_cached(const FifoEnt& h) const {
+    if constexpr (kApp != SGN_TRAFFIC_TGEN) return false;
+    const uint32_t hp = h.count == 1 ? (h.pay >> 16) : (h.pay & 0xFFFFu);
+    return h.dst == ro_dst && h.tag == ro_tag && hp == ro_pay && ro_dst != gid && !(SK(qdisc_rr) && fq_len > 1);
+  }
   __device__ __forceinline__ void forward_out_step() {
     DGT_BEGIN(tf0);
     const bool boot = now < SK(boot_end);
@@ -1886,6 +1900,7 @@ struct HostExec {
     if (cached || fq_len > 0) {
       FifoEnt e;
       bool rr = false;
+      bool merge = false;  // the cached packet and the head entry's run together
       uint32_t run = 1, payload;
       if (cached) {
         fl &= ~F_RO_NEXT;
@@ -1893,6 +1908,16 @@ struct HostExec {
         e.tag = ro_tag;
         e.count = 1;
         payload = ro_pay;
+        if constexpr (kApp == SGN_TRAFFIC_TGEN) {
+          if (fq_len > 0) {
+            const FifoEnt h = fifo_head();
+            if (merges_cached(h)) {
+              merge = true;
+              e = h;
+              run = h.count == 1 ? 2u : h.count;  // the cached packet + the run
+            }
+          }
+        }
       } else {
         e = fifo_head();
         // round-robin qdisc with other sockets waiting: one packet, then this socket goes to
@@ -1921,12 +1946,16 @@ struct HostExec {
           deliver_local(p);
         }
       } else {
-        send_batch(e.dst, payload, e.tag, n_ok, !cached);  // (the cached packet was popped before)
+        // (the cached packet was popped before)
+        send_batch(e.dst, payload, e.tag, n_ok, merge ? 1u : cached ? NO_POP : 0u);
       }
+      // a cached packet alone is not in the send queue, and a merged step that sent nothing
+      // leaves the queue as it is (the cached packet stays cached)
+      const bool outq = cached && !(merge && n_ok > 0);
       // the packet the bucket refused was popped too: it waits in Relay::next_packet
-      if (tr() && blocked && !cached) trace_pop(e.dst, payload, e.tag);
-      const uint32_t consumed = n_ok + (blocked ? 1u : 0u);
-      if (cached) {
+      if (tr() && blocked && !outq) trace_pop(e.dst, payload, e.tag);
+      const uint32_t consumed = n_ok + (blocked ? 1u : 0u) - (merge ? 1u : 0u);
+      if (outq) {
         // not in the send queue
       } else if (consumed == e.count) {
         fq_head = fq_head + 1 == SK(fifo_cap) ? 0 : fq_head + 1;
@@ -2144,7 +2173,13 @@ struct HostExec {
       // over, diag build). Waiting changes nothing of the host's own sequence: `now` is fixed
       // inside the forwarding task, and other lanes are other hosts.
       if constexpr (kApp == SGN_TRAFFIC_TGEN) {
-        const bool lng = !(fl & F_RO_NEXT) && fq_len > 0 && fifo_head().count > kTrainWait;
+        // (a cached packet that the head run continues goes out with it: the step's length
+        // is then the entry's count as well)
+        bool lng = false;
+        if (fq_len > 0) {
+          const FifoEnt h = fifo_head();
+          lng = h.count > kTrainWait && (!(fl & F_RO_NEXT) || merges_cached(h));
+        }
         if (lng && __ballot(1) != act) continue;
       }
       // Forwarding side by side (PERIODIC, waves with many lanes in their loops — config D, where
