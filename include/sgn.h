@@ -362,9 +362,9 @@ typedef int (*sgn_read_fn)(void* user, void* data, size_t len);
  * in one forward pass: header and table, the sections, the trailer. Neither the simulation nor the
  * snapshot changes. Device sections are digested on the device before they leave and stream
  * through two pinned staging chunks, so host memory stays bounded whatever the snapshot's size.
- * Trace records [0, min(trace count at the save, capacity)) are taken from the context's trace
- * buffer (append-only, and the engine is deterministic: they are still there). bytes (may be
- * NULL): the file's length. */
+ * Trace records [b, min(trace count at the save, b + capacity)) are taken from the context's trace
+ * buffer (the engine is deterministic: they are still there), b the records sgn_trace_take has
+ * handed out, 0 without a take; the header carries b. bytes (may be NULL): the file's length. */
 int sgn_snapshot_export(sgn_ctx* ctx, const sgn_snapshot* snap, sgn_write_fn write, void* user, uint64_t* bytes);
 
 /* Builds a new snapshot owned by ctx from a stream, as if sgn_snapshot_save had just taken it here
@@ -470,8 +470,61 @@ typedef struct sgn_trace_rec {
                         send_packet past the DNS check; sgn_rng_* draws count too) */
 } sgn_trace_rec;
 int sgn_trace_enable(sgn_ctx* ctx, uint64_t capacity);
-/* Copies up to cap records (unordered; sort by (host, seq)). n_total = records produced. */
+/* Copies up to cap records (unordered; sort by (host, seq)). n_total = records produced. After
+ * sgn_trace_take (below) the copy holds the records still in the buffer: those produced since
+ * the last take. */
 int sgn_trace_read(sgn_ctx* ctx, sgn_trace_rec* out, uint64_t cap, uint64_t* n_total);
+
+/* ---- additions to ABI 10 (new calls only; no struct of ABI 10 changes): a trace of chosen hosts,
+ * taken out in ordered pieces while the simulation runs. The reference's only network-level
+ * output is the per-host capture (host_options.pcap_enabled, pcap_capture_size:
+ * core/configuration.rs:602-621, interface.rs:192-215); with these calls a capture of a few hosts
+ * of a large, long run needs a trace buffer for one interval only. ----
+ *
+ * sgn_trace_hosts: after sgn_trace_enable and before sgn_sim_init (SGN_ESTATE otherwise), the
+ * HostIds whose records the trace keeps, in any order; only they produce records, advance seq and
+ * keep rng_pos, and their records are exactly those of an unrestricted trace of the same
+ * simulation (every field). A repeated id is SGN_EINVAL here, an id >= n_hosts SGN_EINVAL at
+ * sgn_sim_init. n = 0 removes the set (every host is traced). Every shard of a sharded run passes
+ * the same list and records the hosts it owns. The set is part of a snapshot file's identity when
+ * one is given. */
+int sgn_trace_hosts(sgn_ctx* ctx, const uint32_t* hosts, uint32_t n);
+
+/* Records produced and not yet taken. */
+int sgn_trace_pending(sgn_ctx* ctx, uint64_t* n);
+
+/* One host's records inside a take: out[first .. first + count). */
+typedef struct sgn_trace_span {
+  uint32_t host, reserved;
+  uint64_t first, count;
+} sgn_trace_span;
+
+/* Between calls (like sgn_drain): moves every record produced and not yet taken into out, sorted
+ * by (host, seq) on the device, and empties the trace buffer — its whole capacity is free again,
+ * so sgn_trace_enable's capacity need only hold what one interval between two takes produces
+ * (more is SGN_EOVERFLOW at the round, as without takes). spans (may be NULL) gets one entry per
+ * host with records, ascending by host. All or nothing: with cap below the pending count, or
+ * span_cap below the hosts with records, SGN_ERANGE, *n_out and *n_spans say what is needed and
+ * nothing is taken. The simulation does not change (window, counters and digests are those of a
+ * run without takes). SGN_EDEVICE when a host's pending records do not carry consecutive seq (the
+ * message names the host; nothing is taken).
+ * Snapshots: sgn_snapshot_restore sets the records produced back to the save's count N, and the
+ * taken count too when it was above N — the re-run produces those records again and they are taken
+ * again (the rule of drain records the caller already took). sgn_snapshot_export writes the
+ * records [b, N) still held, b = min(taken, N); the file's header carries b, and a restore of the
+ * imported snapshot leaves exactly those pending (the importing context's buffer must hold N - b
+ * records). */
+int sgn_trace_take(sgn_ctx* ctx, sgn_trace_rec* out, uint64_t cap, uint64_t* n_out, sgn_trace_span* spans,
+                   uint64_t span_cap, uint64_t* n_spans);
+
+/* What the context's last sgn_trace_take spent (measurements; tools/capture_timing.py). */
+typedef struct sgn_trace_take_timing {
+  double total_ms;      /* wall time of the call */
+  double kernel_ms[3];  /* HIP-event times: per-host count and seq range, scan and spans, scatter */
+  double copy_ms;       /* HIP-event time of the device-to-host copies */
+  uint64_t records, hosts;
+} sgn_trace_take_timing;
+int sgn_trace_take_timing_get(sgn_ctx* ctx, sgn_trace_take_timing* out);
 
 /* ------------------------------------------------------------------------------------ */
 /* CPU-resident applications (SGN_TRAFFIC_EXTERNAL)                                      */
@@ -768,6 +821,13 @@ uint32_t sgn_packet_bytes(uint32_t src_ip, uint32_t dst_ip, uint32_t payload_len
  * an unknown peer's address is the record's c. Returns the number of packets written. */
 int64_t sgn_trace_pcap(const sgn_trace_rec* recs, uint64_t n, uint32_t host, const uint32_t* host_ip,
                        uint32_t n_hosts, const char* path, uint32_t capture_len);
+/* (addition to ABI 10) The same packets appended to an open writer, with the writer's capture
+ * length: sgn_trace_pcap is sgn_pcap_open + this + sgn_pcap_close. A capture written piece by
+ * piece (one call per sgn_trace_take, the pieces in the order they were taken) has the bytes of
+ * one written from the whole trace. Returns the packets written, SGN_EINVAL for a null argument
+ * or a peer outside [0, n_hosts). */
+int64_t sgn_pcap_write_trace(sgn_pcap* p, const sgn_trace_rec* recs, uint64_t n, uint32_t host,
+                             const uint32_t* host_ip, uint32_t n_hosts);
 
 /* ------------------------------------------------------------------------------------ */
 /* Test hooks (not part of the reference interface)                                      */

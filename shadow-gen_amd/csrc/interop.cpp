@@ -193,10 +193,11 @@ int sgn_trace_read(sgn_ctx* ctx, sgn_trace_rec* out, uint64_t cap, uint64_t* n_t
   if (!ctx) return SGN_EINVAL;
   if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
   int rc = sync_ctrl(ctx);
-  const uint64_t n = std::min<uint64_t>(ctx->h_ctrl->trace_n, ctx->S.trace_cap);
+  // (the records still in the buffer: all of them until the first sgn_trace_take)
+  const uint64_t n = trace_held(ctx, ctx->h_ctrl->trace_n);
   if (n_total) *n_total = ctx->h_ctrl->trace_n;
   const uint64_t k = std::min(n, cap);
-  if (k && out) SGN_HIP(ctx, hipMemcpy(out, ctx->S.trace, k * sizeof(sgn_trace_rec), hipMemcpyDeviceToHost));
+  if (k && out) SGN_HIP(ctx, hipMemcpy(out, ctx->trace_buf, k * sizeof(sgn_trace_rec), hipMemcpyDeviceToHost));
   return rc;
 }
 

@@ -108,28 +108,31 @@ uint32_t sgn_packet_bytes(uint32_t src_ip, uint32_t dst_ip, uint32_t payload_len
   return total;
 }
 
-int64_t sgn_trace_pcap(const sgn_trace_rec* recs, uint64_t n, uint32_t host, const uint32_t* host_ip,
-                       uint32_t n_hosts, const char* path, uint32_t capture_len) {
-  if ((!recs && n) || !host_ip || host >= n_hosts) return SGN_EINVAL;
+int64_t sgn_pcap_write_trace(sgn_pcap* p, const sgn_trace_rec* recs, uint64_t n, uint32_t host,
+                             const uint32_t* host_ip, uint32_t n_hosts) {
+  if (!p || !p->f || (!recs && n) || !host_ip || host >= n_hosts) return SGN_EINVAL;
+  const uint32_t capture_len = p->capture_len;
   std::vector<const sgn_trace_rec*> mine;
+  bool sorted = true;
   for (uint64_t i = 0; i < n; i++)
     if (recs[i].host == host &&
-        (recs[i].kind == SGN_TRACE_IF_POP || recs[i].kind == SGN_TRACE_DELIVER || recs[i].kind == SGN_TRACE_LOCAL))
+        (recs[i].kind == SGN_TRACE_IF_POP || recs[i].kind == SGN_TRACE_DELIVER || recs[i].kind == SGN_TRACE_LOCAL)) {
+      sorted = sorted && (mine.empty() || mine.back()->seq < recs[i].seq);
       mine.push_back(&recs[i]);
-  std::sort(mine.begin(), mine.end(), [](const sgn_trace_rec* a, const sgn_trace_rec* b) { return a->seq < b->seq; });
-  sgn_pcap* p = nullptr;
-  int rc = sgn_pcap_open(path, capture_len, &p);
-  if (rc) return rc;
+    }
+  // (a span of sgn_trace_take is in seq order already)
+  if (!sorted)
+    std::sort(mine.begin(), mine.end(), [](const sgn_trace_rec* a, const sgn_trace_rec* b) { return a->seq < b->seq; });
   std::vector<uint8_t> buf;
   const uint32_t me = host_ip[host];
   for (const sgn_trace_rec* r : mine) {
     const uint32_t payload = (uint32_t)r->b, tag = (uint32_t)(r->b >> 32);
     uint32_t src = me, dst = me;
     if (r->kind == SGN_TRACE_IF_POP) {
-      if (r->peer != 0xFFFFFFFFu && r->peer >= n_hosts) { sgn_pcap_close(p); return SGN_EINVAL; }
+      if (r->peer != 0xFFFFFFFFu && r->peer >= n_hosts) return SGN_EINVAL;
       dst = r->peer == 0xFFFFFFFFu ? (uint32_t)r->c : host_ip[r->peer];
     } else if (r->kind == SGN_TRACE_DELIVER) {
-      if (r->peer >= n_hosts) { sgn_pcap_close(p); return SGN_EINVAL; }
+      if (r->peer >= n_hosts) return SGN_EINVAL;
       src = host_ip[r->peer];
     }
     const uint32_t len = sgn_packet_bytes(src, dst, payload, tag, nullptr, 0);
@@ -144,10 +147,20 @@ int64_t sgn_trace_pcap(const sgn_trace_rec* recs, uint64_t n, uint32_t host, con
     const uint32_t cap = std::min(len, capture_len);
     bool ok = put(p->f, ts_sec) && put(p->f, ts_usec) && put(p->f, cap) && put(p->f, len);
     if (ok && cap) ok = std::fwrite(buf.data(), 1, cap, p->f) == cap;
-    if (!ok) { sgn_pcap_close(p); return SGN_EDEVICE; }
+    if (!ok) return SGN_EDEVICE;
   }
+  return (int64_t)mine.size();
+}
+
+int64_t sgn_trace_pcap(const sgn_trace_rec* recs, uint64_t n, uint32_t host, const uint32_t* host_ip,
+                       uint32_t n_hosts, const char* path, uint32_t capture_len) {
+  if ((!recs && n) || !host_ip || host >= n_hosts) return SGN_EINVAL;
+  sgn_pcap* p = nullptr;
+  int rc = sgn_pcap_open(path, capture_len, &p);
+  if (rc) return rc;
+  const int64_t k = sgn_pcap_write_trace(p, recs, n, host, host_ip, n_hosts);
   rc = sgn_pcap_close(p);
-  return rc ? rc : (int64_t)mine.size();
+  return k < 0 ? k : rc ? rc : k;
 }
 
 }  // extern "C"

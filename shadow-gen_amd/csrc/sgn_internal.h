@@ -263,6 +263,9 @@ enum : uint32_t {
   F_RO_CONT = 0x800u,        // inside relay_inet_out's forwarding task (never stored)
   F_FH_DIRTY = 0x1000u,      // the send queue's head exists only in LDS (never stored)
   F_COLD = 0x2000u,          // the record's cold lines hold the host's state (else: idle defaults)
+  F_TRACED = 0x4000u,        // the host is traced: every host of a traced simulation, or those that
+                             // sgn_trace_hosts listed (constant from sgn_sim_init; read only by the
+                             // traced k_execute)
 };
 
 enum { SLOT_RO = 0, SLOT_RI = 1, SLOT_APP = 2, NSLOT = 3 };
@@ -738,6 +741,15 @@ struct sgn_ctx {
   bool ctrl_fresh = false;      // h_ctrl is the device's control block (set by sgn_run; cleared by
                                 // every call that may change it)
   uint64_t trace_cap = 0;
+  // the trace taken in pieces (trace_take.hip): Ctrl::trace_n counts every record produced and
+  // trace_base those sgn_trace_take handed out; record p lives at trace_buf[p - trace_base], so the
+  // kernels' view is DevSim::trace = trace_buf - trace_base, DevSim::trace_cap = trace_base + trace_cap
+  sgn_trace_rec* trace_buf = nullptr;
+  uint64_t trace_base = 0;
+  std::vector<uint32_t> trace_hosts;      // sgn_trace_hosts (empty: every host is traced)
+  void* take_mem = nullptr;               // sgn_trace_take's scratch (staging records, per-host words)
+  size_t take_bytes = 0;
+  sgn_trace_take_timing take_timing{};    // of the last sgn_trace_take
   uint64_t drain_cap = 0;                 // sgn_drain_enable (EXTERNAL traffic)
   std::vector<uint64_t> handles;          // sgn_submit handles by slot (tag & ~SGN_TAG_EXT)
   std::vector<uint32_t> submit_seq;       // per owned host: submissions so far
@@ -931,6 +943,17 @@ int grow_codel(sgn_ctx* ctx, uint64_t extra);
 int grow_exchange_slot(sgn_ctx* ctx);  // larger exchange slots (runs past a slot)
 int resolve_hold(sgn_ctx* ctx);        // a held round edge's pool growth
 int inject_runs(sgn_ctx* ctx, const std::vector<EvRec>& runs);  // into the calendar
+// ---- trace_take.hip: the trace buffer as the kernels see it ----
+// DevSim::trace / trace_cap from trace_buf, trace_cap and the cursor `base`, on the host and on the
+// device (every caller changes the cursor between launches, with the stream idle)
+int trace_view_set(sgn_ctx* ctx, uint64_t base);
+// records of the context's trace buffer that a reader may copy now: [trace_base, min(n, trace_base
+// + trace_cap)) for a control block that counts n (n below the cursor: none)
+inline uint64_t trace_held(const sgn_ctx* ctx, uint64_t n) {
+  if (!ctx->trace_buf || n <= ctx->trace_base) return 0;
+  const uint64_t k = n - ctx->trace_base;
+  return k < ctx->trace_cap ? k : ctx->trace_cap;
+}
 }  // namespace sgn
 
 // Every object of libsgn is compiled against this header. A library linked from objects built
@@ -951,6 +974,7 @@ uint64_t layout_sig_run();
 uint64_t layout_sig_pools();
 uint64_t layout_sig_interop();
 uint64_t layout_sig_snapshot_file();
+uint64_t layout_sig_trace_take();
 }  // namespace sgn
 
 #define SGN_HIP(ctx, call)                                   \

@@ -147,6 +147,11 @@ void free_sim(sgn_ctx* ctx) {
   if (ctx->d_rng_stage) hipFree(ctx->d_rng_stage);
   ctx->d_rng_stage = nullptr;
   ctx->rng_stage_cap = 0;
+  if (ctx->take_mem) hipFree(ctx->take_mem);
+  ctx->take_mem = nullptr;
+  ctx->take_bytes = 0;
+  ctx->trace_buf = nullptr;  // (in allocs)
+  ctx->trace_base = 0;
   for (void* p : ctx->allocs) hipFree(p);
   ctx->allocs.clear();
   ctx->sim_bytes = 0;
@@ -173,6 +178,20 @@ int sgn_trace_enable(sgn_ctx* ctx, uint64_t capacity) {
   if (!ctx) return SGN_EINVAL;
   if (ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "sgn_trace_enable must precede sgn_sim_init");
   ctx->trace_cap = capacity;
+  if (!capacity) ctx->trace_hosts.clear();  // (no trace: no set of traced hosts either)
+  return 0;
+}
+
+int sgn_trace_hosts(sgn_ctx* ctx, const uint32_t* hosts, uint32_t n) {
+  if (!ctx || (!hosts && n)) return ctx ? set_error(ctx, SGN_EINVAL, "sgn_trace_hosts: null argument") : SGN_EINVAL;
+  if (ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "sgn_trace_hosts must precede sgn_sim_init");
+  if (!ctx->trace_cap) return set_error(ctx, SGN_ESTATE, "sgn_trace_hosts needs a trace (sgn_trace_enable first)");
+  std::vector<uint32_t> v(hosts, hosts + n);
+  std::sort(v.begin(), v.end());
+  for (uint32_t i = 1; i < n; i++)
+    if (v[i] == v[i - 1])
+      return set_error(ctx, SGN_EINVAL, "sgn_trace_hosts: host " + std::to_string(v[i]) + " is listed twice");
+  ctx->trace_hosts = std::move(v);  // (ascending: the identity digest does not depend on the caller's order)
   return 0;
 }
 
@@ -200,6 +219,9 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
     return set_error(ctx, SGN_EINVAL, "TGEN traffic needs servers");
   if (tr->kind == SGN_TRAFFIC_TGEN && tr->req_payload > 0xFFFFu)
     return set_error(ctx, SGN_EINVAL, "req_payload must fit a UDP datagram");
+  if (ctx->trace_cap && !ctx->trace_hosts.empty() && ctx->trace_hosts.back() >= ctx->n_all)
+    return set_error(ctx, SGN_EINVAL, "sgn_trace_hosts: host " + std::to_string(ctx->trace_hosts.back()) +
+                                          " is not in the simulation (" + std::to_string(ctx->n_all) + " hosts)");
   if (ctx->sim_ready) free_sim(ctx);
   SGN_HIP(ctx, hipSetDevice(ctx->device));
 
@@ -232,7 +254,10 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
     S.cq_pages = (uint32_t)pages;
     S.div_cq.init(pages);
   }
-  S.trace_on = ctx->trace_cap > 0;
+  // 1: every host is traced; 2: the hosts of sgn_trace_hosts (host code reads it: which k_execute
+  // to launch, a snapshot file's identity; the kernel tests F_TRACED in the host's flags)
+  const bool trace_some = ctx->trace_cap && !ctx->trace_hosts.empty();
+  S.trace_on = ctx->trace_cap ? (trace_some ? 2u : 1u) : 0u;
   S.tkind = tr->kind;
   S.payload_len = tr->payload_len;
   S.unknown_permille = tr->unknown_dst_permille;
@@ -335,6 +360,8 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
     r.cq_head = h * CQ_PAGE;  // CoDel chain: page h
     r.cq_tp = h;
     if (is_server[g]) r.flags |= F_SERVER;
+    if (ctx->trace_cap && (!trace_some || std::binary_search(ctx->trace_hosts.begin(), ctx->trace_hosts.end(), g)))
+      r.flags |= F_TRACED;  // (what the traced k_execute tests: every host, or the listed ones)
     const bool has_app = tr->kind == SGN_TRAFFIC_PERIODIC || (tr->kind == SGN_TRAFFIC_TGEN && !is_server[g]);
     if (has_app) {
       r.flags |= F_HAS_APP;
@@ -493,8 +520,10 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
     }
   }
   if (ctx->trace_cap) {
-    S.trace = (decltype(S.trace))dalloc<sgn_trace_rec>(ctx, ctx->trace_cap);
-    if (!S.trace) return set_error(ctx, SGN_ENOMEM, "device allocation failed (trace)");
+    ctx->trace_buf = dalloc<sgn_trace_rec>(ctx, ctx->trace_cap);
+    if (!ctx->trace_buf) return set_error(ctx, SGN_ENOMEM, "device allocation failed (trace)");
+    ctx->trace_base = 0;  // (nothing taken: the kernels' view is the buffer itself)
+    S.trace = (decltype(S.trace))ctx->trace_buf;
     S.trace_cap = ctx->trace_cap;
   }
   ctx->handles.clear();

@@ -540,7 +540,22 @@ int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
        d2d((void*)S.spill, s->spill) && d2d((void*)S.spill_idx, s->spill_idx) && d2d((void*)S.drain, s->drain);
   // an imported snapshot brings the trace records up to its save (import checked that they fit);
   // one saved here has none: this context's trace buffer still holds them
-  if (s->trace.bytes) ok = ok && S.trace && s->trace.bytes <= S.trace_cap * sizeof(sgn_trace_rec) && d2d((void*)S.trace, s->trace);
+  // The cursor of sgn_trace_take: an imported snapshot's records [b, N) go to the buffer's start
+  // and b is the cursor; for one saved here the records [trace_base, N) are still pending, unless
+  // a take since the save moved the cursor past N — then it goes back to N, and the re-run
+  // produces the records from N on again (they are taken again, like drain records already taken).
+  if (ctx->trace_buf) {
+    uint64_t base = std::min<uint64_t>(ctx->trace_base, s->ctrl.trace_n);
+    if (s->trace.bytes) {
+      ok = ok && s->trace.bytes <= ctx->trace_cap * sizeof(sgn_trace_rec) && d2d((void*)ctx->trace_buf, s->trace);
+      base = s->trace_b;
+    } else if (s->imported) {
+      base = s->trace_b;  // (a file without records: everything up to N was taken before its export)
+    }
+    if (ok && base != ctx->trace_base) ok = trace_view_set(ctx, base) == 0;
+  } else {
+    ok = ok && s->trace.bytes == 0;
+  }
   if (ok && s->runs) {
     // (the fills just restored, in stream order; the same scan as at save: the same offsets)
     launch_scan(st, sc, (const uint32_t*)S.slab_n, (const uint64_t*)S.ext, S.CAP, n_slabs);

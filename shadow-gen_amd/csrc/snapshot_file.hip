@@ -134,7 +134,9 @@ struct FileHeader {
       codel_allocs_before;
   uint64_t calendar_runs, trace_records;
   uint64_t n_sections, file_bytes;
-  uint64_t reserved;  // 0 (keeps the header a multiple of 16 bytes)
+  uint64_t reserved;  // the trace records sgn_trace_take had handed out before the export: the
+                      // section holds the records from this one on (0 without a take: the spare
+                      // word that keeps the header a multiple of 16 bytes)
 };
 static_assert(sizeof(FileHeader) % 16 == 0, "the table and the payloads start 16-byte aligned");
 struct TableEnt {
@@ -262,6 +264,13 @@ int identity(sgn_ctx* ctx, uint64_t* out) {
                      (uint64_t)S.U, (uint64_t)S.NB, S.BW, (uint64_t)S.G, (uint64_t)S.gsh, (uint64_t)S.fifo_cap, S.drain_cap,
                      S.min_possible, S.max_lat})
     v.push_back(x);
+  // the traced hosts, only when sgn_trace_hosts gave a set (a simulation without one keeps the
+  // identity it had before the call existed): their records, seq and rng_pos differ with the set
+  if (S.trace_on == 2u) {
+    v.push_back(0x7472616365686f73ull);  // "tracehos"
+    v.push_back(ctx->trace_hosts.size());
+    v.push_back(sgn_digest_bytes(ctx->trace_hosts.data(), ctx->trace_hosts.size() * 4));
+  }
   ctx->identity = sgn_digest_bytes(v.data(), v.size() * 8);
   ctx->identity_gen = ctx->sim_gen;
   *out = ctx->identity;
@@ -350,10 +359,14 @@ int export_one(sgn_ctx* ctx, sgn_snapshot* s, sgn_write_fn wr, void* user, uint6
   FileHeader h;
   header_base(ctx, &h);
   if (int rc = identity(ctx, &h.identity)) return rc;
-  // the trace records up to the save: an imported snapshot's own, else the context's (append-only)
-  const uint64_t n_trace = s->trace.bytes ? s->trace.bytes / sizeof(sgn_trace_rec)
-                                          : (ctx->S.trace ? std::min<uint64_t>(s->ctrl.trace_n, ctx->S.trace_cap) : 0);
-  const void* trace = s->trace.bytes ? s->trace.d : (const void*)ctx->S.trace;
+  // the trace records up to the save that sgn_trace_take has not handed out, [b, N): an imported
+  // snapshot's own, else the context's — record p is at trace_buf[p - trace_base], so they start
+  // the buffer (b = trace_base) or there are none (a take since the save passed N: b = N). Without
+  // a take b = 0 and the section is the records [0, N), as before the call existed.
+  const uint64_t trace_b = s->imported ? s->trace_b : std::min<uint64_t>(ctx->trace_base, s->ctrl.trace_n);
+  const uint64_t n_trace = s->imported ? s->trace.bytes / sizeof(sgn_trace_rec)
+                                       : (ctx->trace_buf ? std::min<uint64_t>(s->ctrl.trace_n - trace_b, ctx->trace_cap) : 0);
+  const void* trace = s->imported ? s->trace.d : (const void*)ctx->trace_buf;
   const std::vector<Sec> secs = sections_of(s, trace, n_trace);
   std::vector<uint64_t> dig;
   float dig_ms = 0;
@@ -378,6 +391,7 @@ int export_one(sgn_ctx* ctx, sgn_snapshot* s, sgn_write_fn wr, void* user, uint6
   h.codel_allocs_before = s->codel_allocs_before;
   h.calendar_runs = s->runs;
   h.trace_records = n_trace;
+  h.reserved = trace_b;
   h.n_sections = secs.size();
   std::vector<TableEnt> tab(secs.size());
   uint64_t total = sizeof(FileHeader) + secs.size() * sizeof(TableEnt) + 8;
@@ -497,7 +511,7 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
                                               " has " + std::to_string(f.want));
   }
   // the trace: records need a buffer that holds them (and a traced simulation's sections differ)
-  if (h.traced != want.traced || (h.trace_records && (!S.trace || S.trace_cap < h.trace_records)))
+  if (h.traced != want.traced || (h.trace_records && (!ctx->trace_buf || ctx->trace_cap < h.trace_records)))
     return set_error(ctx, SGN_ESTATE, w + (h.traced ? "the file has trace records and this context's trace buffer does not hold them "
                                                         "(sgn_trace_enable before sgn_sim_init)"
                                                       : "the file is of an untraced simulation and this context keeps a trace"));
@@ -630,7 +644,9 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
   if (c.keep_slab > S.NB) return fail(SGN_EFILE, w + "the control block's spare slab is outside the calendar");
   if (s->drain.bytes != (S.drain ? std::min<uint64_t>(c.drain_n, S.drain_cap) : 0) * sizeof(sgn_drain_rec))
     return fail(SGN_EFILE, w + "section drain does not hold the control block's record count");
-  if (h.trace_records > c.trace_n) return fail(SGN_EFILE, w + "more trace records than the control block counts");
+  // (the section holds the records [reserved, trace_n) that sgn_trace_take had not handed out)
+  if (h.reserved > c.trace_n || h.trace_records > c.trace_n - h.reserved || (!h.traced && h.reserved))
+    return fail(SGN_EFILE, w + "more trace records than the control block counts");
   {  // the extension table: every extension inside the extension pool
     uint64_t n_ext = 0;
     for (uint64_t e : s->h_ext) {
@@ -666,6 +682,8 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
   s->S.ext_total = h.ext_total;
   s->S.gspec = (uint32_t)h.gspec;
   s->runs = h.calendar_runs;
+  s->imported = true;
+  s->trace_b = h.reserved;
   s->rounds_enqueued = h.rounds_enqueued;
   s->codel_grows = h.codel_grows;
   s->cal_grows = h.cal_grows;

@@ -23,9 +23,12 @@ struct sgn_snapshot {
   Buf codel, cq_next, cq_free, spill, spill_idx;  // the pools that grow
   Buf drain;                                      // undrained records [0, drain_n)
   Buf packed;                                     // the calendar's runs
-  Buf trace;                                      // imported snapshots only: trace records [0, trace_n)
+  Buf trace;                                      // imported snapshots only: trace records [trace_b, trace_n)
                                                   // (sgn_snapshot_save leaves it empty: in its own
                                                   // context the records are still in the trace buffer)
+  bool imported = false;                          // built by sgn_snapshot_import
+  uint64_t trace_b = 0;                           // imported: records sgn_trace_take had handed out
+                                                  // before the export (the file's first record)
   uint64_t runs = 0;
   // host-side simulation state
   uint64_t rounds_enqueued = 0;

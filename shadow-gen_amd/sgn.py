@@ -122,6 +122,20 @@ class TraceRec(C.Structure):
 TRACE_DTYPE = np.dtype([("kind", "<u4"), ("host", "<u4"), ("peer", "<u4"), ("flags", "<u4"),
                         ("a", "<u8"), ("b", "<u8"), ("c", "<u8"), ("seq", "<u8"), ("rng_pos", "<u8")])
 TRACE_SEND, TRACE_POP, TRACE_DELIVER, TRACE_CODEL_DROP, TRACE_IF_POP, TRACE_LOCAL = 1, 2, 3, 4, 5, 6
+class TraceSpan(C.Structure):
+    _fields_ = [("host", C.c_uint32), ("reserved", C.c_uint32), ("first", C.c_uint64), ("count", C.c_uint64)]
+
+
+SPAN_DTYPE = np.dtype([("host", "<u4"), ("reserved", "<u4"), ("first", "<u8"), ("count", "<u8")])
+assert SPAN_DTYPE.itemsize == C.sizeof(TraceSpan)
+ERANGE = -34
+
+
+class TraceTakeTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_double), ("kernel_ms", C.c_double * 3), ("copy_ms", C.c_double),
+                ("records", C.c_uint64), ("hosts", C.c_uint64)]
+
+
 DIGEST_DTYPE = np.dtype([("tx", "<u8"), ("rx", "<u8"), ("app", "<u8"), ("rng", "<u8", (4,)),
                          ("next_event_id", "<u8"), ("n_sent", "<u8"), ("n_popped", "<u8"),
                          ("n_delivered", "<u8"), ("n_codel_dropped", "<u8")])
@@ -323,6 +337,11 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         "sgn_snapshot_file_timing_get": (C.c_int, [vp, C.POINTER(SnapshotFileTiming)]),
         "sgn_digest_bytes": (C.c_uint64, [vp, C.c_size_t]),
         "sgn_selftest_digest": (C.c_int, [vp, vp, C.c_size_t, u64p]),
+        "sgn_trace_hosts": (C.c_int, [vp, u32p, C.c_uint32]),
+        "sgn_trace_pending": (C.c_int, [vp, u64p]),
+        "sgn_trace_take": (C.c_int, [vp, C.POINTER(TraceRec), C.c_uint64, u64p, C.POINTER(TraceSpan), C.c_uint64, u64p]),
+        "sgn_trace_take_timing_get": (C.c_int, [vp, C.POINTER(TraceTakeTiming)]),
+        "sgn_pcap_write_trace": (C.c_int64, [vp, C.POINTER(TraceRec), C.c_uint64, C.c_uint32, u32p, C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -583,11 +602,51 @@ class Context:
         return out
 
     def trace(self):
+        """The records in the trace buffer, unordered: all of them, or after trace_take() those
+        produced since the last take."""
         n = C.c_uint64()
-        self.check(self.L.sgn_trace_read(self.h, None, 0, C.byref(n)))
+        self.check(self.L.sgn_trace_pending(self.h, C.byref(n)))
         out = np.zeros(n.value, dtype=TRACE_DTYPE)
         self.check(self.L.sgn_trace_read(self.h, out.ctypes.data_as(C.POINTER(TraceRec)), n.value, C.byref(n)))
         return out
+
+    # ---- a trace of chosen hosts, taken out in ordered pieces (sgn_trace_hosts / _take) ----
+    def trace_hosts(self, hosts):
+        """After trace_enable and before sim_init: only these HostIds are traced ([] : all)."""
+        h = np.ascontiguousarray(hosts, dtype=np.uint32)
+        self.check(self.L.sgn_trace_hosts(self.h, ptr(h, C.c_uint32) if len(h) else None, len(h)))
+
+    def trace_pending(self):
+        n = C.c_uint64()
+        self.check(self.L.sgn_trace_pending(self.h, C.byref(n)))
+        return n.value
+
+    def trace_take(self, cap=None, span_cap=None):
+        """(records, spans): every record produced and not yet taken, sorted by (host, seq) on the
+        device, and one span {host, first, count} per host with records (ascending host); the
+        trace buffer is empty afterwards. cap / span_cap: the arrays' sizes (default: what is
+        pending); too small raises SgnError with rc ERANGE, .needed = (records, spans), and takes
+        nothing."""
+        if cap is None:
+            cap = self.trace_pending()
+        if span_cap is None:
+            span_cap = min(cap, self._hosts.n)
+        recs = np.zeros(cap, dtype=TRACE_DTYPE)
+        spans = np.zeros(span_cap, dtype=SPAN_DTYPE)
+        n, ns = C.c_uint64(), C.c_uint64()
+        rc = self.L.sgn_trace_take(self.h, recs.ctypes.data_as(C.POINTER(TraceRec)) if cap else None, cap, C.byref(n),
+                                   spans.ctypes.data_as(C.POINTER(TraceSpan)) if span_cap else None, span_cap, C.byref(ns))
+        if rc != 0:
+            e = SgnError(rc, self.L.sgn_last_error(self.h).decode())
+            e.needed = (n.value, ns.value)
+            raise e
+        return recs[: n.value], spans[: ns.value]
+
+    def trace_take_timing(self):
+        t = TraceTakeTiming()
+        self.check(self.L.sgn_trace_take_timing_get(self.h, C.byref(t)))
+        return {"total_ms": t.total_ms, "kernel_ms": list(t.kernel_ms), "copy_ms": t.copy_ms,
+                "records": t.records, "hosts": t.hosts}
 
     # ---- CPU-resident applications (TRAFFIC_EXTERNAL) and the host RNG ----
     def drain_enable(self, cap):
@@ -842,6 +901,83 @@ def write_pcaps(trace, host_ips, out_dir, names=None, hosts=None, capture_len=65
             raise SgnError(int(n), f"sgn_trace_pcap host {h}")
         out[int(h)] = (path, int(n))
     return out
+
+
+class Capture:
+    """Per-host interface captures written while the simulation runs (host_options.pcap_enabled,
+    interface.rs:45-51): one open writer per captured host at <out_dir>/hosts/<name>/eth0.pcap
+    (<out_dir>/h<id>/eth0.pcap without names), each with its own capture length
+    (pcap_capture_size). feed() appends one trace_take(); the files end up with the bytes
+    write_pcaps gives for the whole trace."""
+
+    def __init__(self, out_dir, host_ips, hosts, capture_sizes=65535, names=None, lib=None):
+        self.L = lib or load()
+        self.ips = np.ascontiguousarray(host_ips, dtype=np.uint32)
+        hosts = [int(h) for h in hosts]
+        sizes = [int(capture_sizes)] * len(hosts) if np.ndim(capture_sizes) == 0 else [int(s) for s in capture_sizes]
+        if len(sizes) != len(hosts):
+            raise ValueError("Capture: one capture size per host")
+        self.writers, self.paths, self.packets = {}, {}, {}
+        try:
+            for h, size in zip(hosts, sizes):
+                d = os.path.join(out_dir, "hosts", names[h]) if names is not None else os.path.join(out_dir, f"h{h}")
+                os.makedirs(d, exist_ok=True)
+                path = os.path.join(d, "eth0.pcap")
+                w = C.c_void_p()
+                rc = self.L.sgn_pcap_open(os.fsencode(path), size, C.byref(w))
+                if rc != 0:
+                    raise SgnError(rc, f"sgn_pcap_open {path}")
+                self.writers[h], self.paths[h], self.packets[h] = w, path, 0
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def hosts(self):
+        return sorted(self.writers)
+
+    def feed(self, records, spans):
+        """Appends one take: spans[i] = {host, first, count} over records (trace_take's pair)."""
+        recs = np.ascontiguousarray(records, dtype=TRACE_DTYPE)
+        for s in spans:
+            h, first, count = int(s["host"]), int(s["first"]), int(s["count"])
+            w = self.writers.get(h)
+            if w is None or count == 0:
+                continue
+            part = recs[first:first + count]
+            n = self.L.sgn_pcap_write_trace(w, part.ctypes.data_as(C.POINTER(TraceRec)), count, h,
+                                            ptr(self.ips, C.c_uint32), len(self.ips))
+            if n < 0:
+                raise SgnError(int(n), f"sgn_pcap_write_trace host {h}")
+            self.packets[h] += int(n)
+
+    def close(self):
+        """Closes the files; returns {host: (path, packets)} like write_pcaps."""
+        err = 0
+        for w in self.writers.values():
+            err = self.L.sgn_pcap_close(w) or err
+        out = {h: (self.paths[h], self.packets[h]) for h in self.writers}
+        self.writers = {}
+        if err:
+            raise SgnError(err, "sgn_pcap_close")
+        return out
+
+
+def run_captured(ctx, capture, step_ns, until=None):
+    """Runs ctx (a Context whose trace_hosts are the capture's hosts) to its end, or until the next
+    window would start at or after `until`, in steps of step_ns of simulated time: run_until, then
+    trace_take, then capture.feed. The trace buffer (trace_enable's capacity) need only hold what
+    one step produces. Returns the rounds run."""
+    rounds = 0
+    while True:
+        ws, _, active = ctx.window()
+        if not active or (until is not None and ws >= until):
+            break
+        t = ws + step_ns
+        rounds += ctx.run_until(t if until is None else min(t, until))
+        capture.feed(*ctx.trace_take())
+    capture.feed(*ctx.trace_take())  # (records produced before the call, if any)
+    return rounds
 
 
 def derive_seeds(sim_seed, names, lib=None):

@@ -824,6 +824,11 @@ class SimSetup:
     qdisc: int
     seed: int
     process_start_ns: list  # per host: start times of its processes (informational)
+    # sim_config.rs:258-270 (HostInfo::pcap_config): the HostIds whose host_options, after
+    # host_option_defaults and the host's own overrides, have pcap_enabled, ascending, and each
+    # one's pcap_capture_size in bytes (sgn.Capture / sgn.run_captured write their eth0.pcap)
+    pcap_hosts: list = field(default_factory=list)
+    pcap_capture_size: list = field(default_factory=list)
 
     def sim_config(self, **engine):
         """sgn_sim_config with the engine capacities (out_fifo_cap, codel_cap, event_capacity ...)
@@ -902,7 +907,10 @@ def sim_setup(cfg: ConfigOptions, base_dir=None, debug_hosts=(), lib=None) -> Si
     seeds = sgn.derive_seeds(g["seed"], names, lib)
     runahead = _denull(cfg.experimental["runahead"])
     boot = g["bootstrap_end_time"]
+    pcap = [(i, int(h["host_options"]["pcap_capture_size"].base()))
+            for i, h in enumerate(cfg.hosts.values()) if h["host_options"]["pcap_enabled"]]
     return SimSetup(
+        pcap_hosts=[i for i, _ in pcap], pcap_capture_size=[s for _, s in pcap],
         names=names, graph=graph, used_nodes=np.unique(node),
         hosts=sgn.HostArrays(ips, node, up, down, seeds),
         use_shortest_path=bool(cfg.network["use_shortest_path"]),
