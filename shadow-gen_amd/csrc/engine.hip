@@ -2328,13 +2328,7 @@ __device__ void finalize_fused(const DevSim& S, uint32_t lane, uint32_t nch, uin
     }
     const uint64_t min_next = m == INVALID ? EMU_MAX : m;  // unwrap_or(MAX)
     st_dev(&C->last_min_next, min_next);
-    // Runahead::get (runahead.rs:44-57)
-    uint64_t ra = (SK(dynamic) && mu != INVALID) ? mu : SK(min_possible);
-    ra = ra > SK(runahead_cfg) ? ra : SK(runahead_cfg);
-    // Controller::manager_finished_current_round (controller.rs:88-112)
-    uint64_t ne = min_next + ra;
-    if (ne < min_next || ne > EMU_MAX) ne = EMU_MAX;
-    ne = ne < SK(end_time) ? ne : SK(end_time);
+    const uint64_t ne = window_end(min_next, mu, SK(dynamic), SK(min_possible), SK(runahead_cfg), SK(end_time));
     st_dev(&C->active, min_next < ne ? 1u : 0u);
     if (min_next < ne) {  // the next round's guards (hold before it runs)
       const uint64_t need = codel_round_bound(S, occ, min_next, ne);
@@ -3319,7 +3313,9 @@ __device__ __forceinline__ RbEdge rb_edge(const SV& S, uint32_t p, uint32_t nch,
   m = e.nb1 < m ? e.nb1 : m;
   m = wn < m ? wn : m;
   e.min_next = m == INVALID ? EMU_MAX : m;  // unwrap_or(MAX)
-  // Runahead::get (runahead.rs:44-57)
+  // window_end's rule (sgn_internal.h), written out: through the function the compiler works it
+  // out on the scalar unit and waits for mu in the middle of the loads above — a second round
+  // trip per round (config C: +0.45 % per step, same-box ABBA)
   uint64_t ra = (SK(dynamic) && mu != INVALID) ? mu : SK(min_possible);
   ra = ra > SK(runahead_cfg) ? ra : SK(runahead_cfg);
   uint64_t ne = e.min_next + ra;
@@ -3352,37 +3348,45 @@ __device__ __forceinline__ void rb_bookkeep(const SV& S, uint64_t ws, uint64_t w
 // queues) belongs to this workgroup's groups.
 // kBig: compiled with the big-slab path (launched while some slab has an extension; without
 // one, the path's code cost config C 2.6 % per launch in same-box A/B, round 4)
-// The persistent kernels' per-launch state, reset by the launch itself (no host memsets before
-// a launch): round buffer 0 (chunk minima, counters of both barriers, spare-slab
-// minimum, freed / allocated / spilled counts, exports) and the idle-gap counter, by the shard's
-// bookkeeping workgroup BEFORE it counts itself into the residency census — every workgroup
-// waits for the whole census, so no arrival can reach the buffers first. Buffers 1 and 2 are
-// reset during rounds 0 and 1 as before.
-template <uint32_t kApp, class SV>
-__device__ __forceinline__ void rb_reset0(const SV& S, uint32_t nch) {
+
+// Round buffer q of a grid of nch chunks, reset by the bookkeeping workgroup: chunk minima and
+// occupancy sums, the counters of both barriers (the grid's chunks, then the top counter; the
+// second barrier's and the exports: k_rounds_x, null in a single shard), the spare-slab minimum
+// and the freed / allocated / spilled counts.
+template <uint32_t kApp, bool kX, class SV>
+__device__ __forceinline__ void rb_reset(const SV& S, uint32_t q, uint32_t nch) {
   using Y = RbLayout<kApp>;
   for (uint32_t i = threadIdx.x; i < nch; i += 64) {
-    st_dev(&SK(rb_min)[(size_t)i * Y::MS], (uint64_t)INVALID);
-    st_dev(&SK(rb_min)[(size_t)i * Y::MS + 1], (uint64_t)INVALID);
-    st_dev(&SK(rb_occ)[(size_t)i * Y::OS], (uint64_t)0);
+    st_dev(&SK(rb_min)[((size_t)q * RB_CH + i) * Y::MS], (uint64_t)INVALID);
+    st_dev(&SK(rb_min)[((size_t)q * RB_CH + i) * Y::MS + 1], (uint64_t)INVALID);
+    st_dev(&SK(rb_occ)[((size_t)q * RB_CH + i) * Y::OS], (uint64_t)0);
   }
   for (uint32_t i = threadIdx.x; i <= nch; i += 64) {
-    const size_t o = (size_t)(i == nch ? RB_CH : i) * Y::CS;
+    const size_t o = (size_t)q * Y::CB + (i == nch ? RB_CH : i) * Y::CS;
     st_dev(&SK(rb_cnt)[o], 0u);
-    if (SK(rb2_cnt)) st_dev(&SK(rb2_cnt)[o], 0u);
+    if constexpr (kX) st_dev(&SK(rb2_cnt)[o], 0u);
   }
-  if (SK(xout_n))
+  if constexpr (kX)
     for (uint32_t i = threadIdx.x; i < SK(n_ranks); i += 64) {
-      st_dev(&SK(xout_n)[i], 0u);
-      st_dev(&SK(xout_n)[3 * SK(n_ranks) + i], 0u);  // (k_rounds_x: the per-peer totals)
+      st_dev(&SK(xout_n)[q * SK(n_ranks) + i], 0u);
+      st_dev(&SK(xout_n)[(3 + q) * SK(n_ranks) + i], 0u);  // (k_rounds_x: the per-peer totals)
     }
   if (threadIdx.x == 0) {
-    st_dev(&SK(rb_keep)[0], (uint64_t)INVALID);
-    st_dev(&SK(rb_free)[0], (uint64_t)0);
-    st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX], (uint64_t)0);
-    st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + 3], (uint64_t)0);
-    st_dev(&SK(rb_cnt)[3 * RB_CB_MAX], 0u);  // the idle-gap barrier's counter
+    st_dev(&SK(rb_keep)[q], (uint64_t)INVALID);
+    st_dev(&SK(rb_free)[q], (uint64_t)0);
+    st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + q], (uint64_t)0);
+    st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + 3 + q], (uint64_t)0);
   }
+}
+// The persistent kernels' per-launch state, reset by the launch itself (no host memsets before
+// a launch): round buffer 0 and the idle-gap counter, by the shard's
+// bookkeeping workgroup BEFORE it counts itself into the residency census — every workgroup
+// waits for the whole census, so no arrival can reach the buffers first. Buffers 1 and 2 are
+// reset during rounds 0 and 1 (buffer (r + 1) % 3 during round r).
+template <uint32_t kApp, bool kX, class SV>
+__device__ __forceinline__ void rb_reset0(const SV& S, uint32_t nch) {
+  rb_reset<kApp, kX>(S, 0, nch);
+  if (threadIdx.x == 0) st_dev(&SK(rb_cnt)[3 * RB_CB_MAX], 0u);  // the idle-gap barrier's counter
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -3431,6 +3435,133 @@ __device__ __forceinline__ decltype(auto) sim_view(const DevSim* __restrict__ Sg
     return (*Sg);
 }
 
+// ---- the steps of a persistent round that k_rounds and k_rounds_x share ----
+// Each kernel keeps its round state in a RoundLDS of its own (k_rounds_x packs its flags into half
+// words and adds the exchange's); the steps below take either one.
+
+// Launch prologue (thread 0): the control block into the workgroup's round state.
+template <class RS>
+__device__ __forceinline__ void round_state_load(RS& rs, SGN_GLB Ctrl* C) {
+  rs.pg_avail = ld_dev(&C->pg_avail);
+  rs.ws = ld_dev(&C->ws);
+  rs.we = ld_dev(&C->we);
+  rs.active = (decltype(rs.active))ld_dev(&C->active);
+  rs.ks = ld_dev(&C->keep_slab);
+  rs.pend = 0;
+  rs.ngap = 0;
+  rs.pg_alloc = ld_dev(&C->pg_alloc);
+  rs.occ = ld_dev(&C->cal_occ);
+  rs.hold = ld_dev(&C->hold);  // (a round still held: the launch returns at once)
+  rs.hold_need = ld_dev(&C->hold_need);
+  rs.pause_at = ld_dev(&C->pause_at);  // (read once: every workgroup decides alike; the host
+                                       // writes every shard the same target)
+}
+
+// Launch epilogue (the bookkeeping workgroup's thread 0): the round state into the host-visible
+// control block. rounds: the control block's round count after this launch; spill_imp
+// (k_rounds_x): the spill-area entries that may hold imported runs.
+template <class RS>
+__device__ __forceinline__ void round_state_store(SGN_GLB Ctrl* C, const RS& rs, uint64_t rounds,
+                                                  const uint64_t* spill_imp) {
+  st_dev(&C->keep_slab, rs.ks);
+  st_dev(&C->ws, rs.ws);
+  st_dev(&C->we, rs.we);
+  st_dev(&C->active, (uint32_t)rs.active);
+  st_dev(&C->rounds, rounds);
+  st_dev(&C->pg_avail, rs.pg_avail);
+  st_dev(&C->cal_occ, rs.occ);
+  if (spill_imp)
+    (void)__hip_atomic_fetch_max(&C->spill_imp, *spill_imp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (rs.hold) {
+    st_dev(&C->hold, rs.hold);
+    st_dev(&C->hold_need, rs.hold_need);
+  }
+}
+
+// Per round (thread 0): the outbox header of round buffer p for the window starting at ws.
+template <class SV>
+__device__ __forceinline__ void ob_round_begin(const SV& S, const ExecLDS& X, uint32_t p, uint64_t ws,
+                                               uint64_t pg_avail) {
+  X.ob->keepmin = &SK(rb_keep)[p];
+  X.ob->bbase = ws;
+  X.ob->pg_avail = pg_avail;
+  X.ob->pg_freed = &SK(rb_free)[p];
+  X.ob->pg_allocd = &SK(rb_occ)[3 * RB_CH * RB_OS_MAX + p];
+  X.ob->spilled = &SK(rb_occ)[3 * RB_CH * RB_OS_MAX + 3 + p];
+}
+
+// The idle gap after the round [ws, we) whose next window ends at nwe. This round's bucket
+// bookkeeping (consumed minima -> INVALID, bucket b1 -> nb1) is done by the bookkeeping workgroup
+// during the next round, with plain stores: safe while the next round's sends cannot reach this
+// round's buckets. They can after an idle gap: a send at t maps to this round's bucket indices
+// again once t >= bucketstart(ws) + NB * BW, and t < nwe + max_lat. Then (every workgroup decides
+// alike) the bookkeeping workgroup does it now and a second grid barrier keeps every send of the
+// next round behind it (a lost bucket minimum). bk: this is the bookkeeping workgroup.
+// Returns whether the gap was taken; timed_out(): what the kernel does when the barrier does not complete.
+template <class SV, class RS, class OnTimeout>
+__device__ __forceinline__ bool gap_barrier(const SV& S, RS& rs, bool bk, uint32_t P, uint64_t ws, uint64_t we,
+                                            uint32_t ks, uint32_t active, uint64_t nwe, uint64_t nb1,
+                                            OnTimeout&& timed_out) {
+  const uint64_t span = (uint64_t)SK(NB) * SK(BW);
+  const uint64_t bstart = SIM_START + SK(bw_div).div(ws - SIM_START) * SK(BW);
+  const bool gap = active && (nwe + SK(max_lat) >= bstart + span || nwe + SK(max_lat) < nwe);
+  if (gap) {
+    if (bk) rb_bookkeep(S, ws, we, nb1, ks);  // (the previous round's: done at this round's start)
+    if (threadIdx.x == 0) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the bookkeeping workgroup's stores are done
+      SGN_GLB uint32_t* gc = SK(rb_cnt) + 3 * RB_CB_MAX;
+      const uint32_t target = (rs.ngap + 1) * P;
+      __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      uint32_t sp = 0;
+      while (ld_dev(gc) < target && ++sp < (1u << 24)) __builtin_amdgcn_s_sleep(2);
+      if (sp >= (1u << 24)) timed_out();
+      rs.ngap++;
+    }
+  }
+  return gap;
+}
+
+// Round end (thread 0), after the barrier: the spare slab set (survivors + this round's new runs
+// for b1 = bucket_of(S, we - 1), the window's last bucket) becomes bucket b1 — in the workgroup's own bucket -> slab
+// table when it keeps one (lds_tab) —, the finished round's bookkeeping is left for the next
+// round's start unless the idle gap did it, the next window [nws, nwe), and the round's freed and
+// allocated pages and occupancy change (all written: barrier).
+template <class SV, class RS>
+__device__ __forceinline__ void round_state_advance(const SV& S, const ExecLDS& X, RS& rs, bool lds_tab, uint32_t b1,
+                                                    uint64_t ws, uint64_t we, uint32_t ks, bool gap, uint64_t nb1,
+                                                    uint64_t nws, uint64_t nwe, uint32_t active, uint64_t nfree,
+                                                    uint64_t nalloc, uint64_t occd) {
+  const uint32_t slab_b1 = lds_tab ? X.lbs[b1] : ld_dev(&SK(bucket_slab)[b1]);
+  if (lds_tab) X.lbs[b1] = (uint16_t)ks;
+  rs.pend = gap ? 0u : 1u;
+  rs.pend_ws = ws;
+  rs.pend_we = we;
+  rs.pend_nb1 = nb1;
+  rs.pend_new = ks;
+  rs.ks = slab_b1;
+  rs.ws = nws;
+  rs.we = nwe;
+  rs.active = active;
+  rs.pg_avail += nfree;
+  rs.pg_alloc += nalloc;
+  rs.occ += occd;
+}
+
+// Launch end: the launch's per-wave statistics, in the slot of this workgroup's first group (the
+// host sums the slots; the mapping is a bijection, so gq0 < G is this workgroup's alone — a forced
+// grid larger than G has workgroups w >= G; one without groups has nothing to flush)
+template <class SV>
+__device__ __forceinline__ void wacc_flush(const SV& S, const ExecLDS& X, uint32_t gq0, uint32_t gq1) {
+  __syncthreads();
+  if (X.wacc && threadIdx.x < W_N && X.wacc[threadIdx.x] && gq0 < gq1) {
+    const uint32_t k = threadIdx.x;
+    if (k == W_MAXFILL)
+      __hip_atomic_fetch_max(&SK(w_cnt)[k * SK(G) + gq0], X.wacc[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else
+      cnt_add(&SK(w_cnt)[k * SK(G) + gq0], X.wacc[k]);
+  }
+}
+
 template <uint32_t kApp, bool kBig, bool kDiag>
 __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint32_t max_rounds, uint32_t epoch,
                                             uint32_t res_base) {
@@ -3448,23 +3579,9 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
     if (threadIdx.x < W_N) wacc_[threadIdx.x] = 0;
   }
   const uint32_t w = blockIdx.x, P = gridDim.x;
-  // The workgroup's groups: [gq0, gq1) in steps of gqs. TGEN: w, w + P, ... (config C's server
-  // groups come first in slot order and set the round's chain: dealt over every XCD). PERIODIC:
-  // XCD-aware — workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8; observed, used
-  // for speed only), so the ones sharing blockIdx % 8 take one contiguous eighth of the groups.
-  // Slots are ordered by graph node (sim_init), so an XCD's hosts cover an eighth of the nodes
-  // and their sends read an eighth of the route table's rows (config D: 2 of 16 MB, L2-resident).
-  // Any fixed bijection works: a group's records belong to its workgroup for the launch.
-  uint32_t gq0 = w, gq1 = SK(G), gqs = P;
-  if constexpr (kApp == SGN_TRAFFIC_PERIODIC) {
-    const uint32_t x = w & 7u, cx = (P - x + 7u) >> 3;  // this class's workgroups
-    uint32_t before = 0;                                 // workgroups of the classes below x
-    for (uint32_t y = 0; y < x; y++) before += (P - y + 7u) >> 3;
-    const uint32_t s0 = (uint32_t)((uint64_t)SK(G) * before / P), s1 = (uint32_t)((uint64_t)SK(G) * (before + cx) / P);
-    gq0 = s0 + (w >> 3);
-    gq1 = s1;
-    gqs = cx;
-  }
+  // the workgroup's groups: [gq0, gq1) in steps of gqs (wg_groups, sgn_internal.h)
+  uint32_t gq0, gq1, gqs;
+  wg_groups<kApp>(SK(G), w, P, gq0, gq1, gqs);
   // Residency census before any simulation state is touched: the grid barrier below needs
   // every workgroup on the chip at once. Each workgroup counts itself in and waits (bounded)
   // for the rest; the first to see the whole grid, or to give up, sets the verdict with a
@@ -3472,7 +3589,7 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
   // leaves untouched and the host runs the rounds with per-round launches instead.
   {
     __shared__ uint32_t verdict;
-    if (w == P - 1) rb_reset0<kApp>(S, (P + 63) >> 6);
+    if (w == P - 1) rb_reset0<kApp, false>(S, (P + 63) >> 6);
     if (threadIdx.x == 0) {
       bool decided;
       verdict = census(C, P, epoch, res_base, &decided);
@@ -3497,19 +3614,8 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
   };
   __shared__ RoundLDS rs;
   if (threadIdx.x == 0) {
-    rs.pg_avail = ld_dev(&C->pg_avail);
-    rs.ws = ld_dev(&C->ws);
-    rs.we = ld_dev(&C->we);
-    rs.active = ld_dev(&C->active);
-    rs.ks = ld_dev(&C->keep_slab);
-    rs.pend = 0;
-    rs.ngap = 0;
-    rs.pg_alloc = ld_dev(&C->pg_alloc);
-    rs.occ = ld_dev(&C->cal_occ);
+    round_state_load(rs, C);
     rs.nspill = ld_dev(&C->spill_n);
-    rs.hold = ld_dev(&C->hold);  // (a round still held: the launch returns at once)
-    rs.hold_need = ld_dev(&C->hold_need);
-    rs.pause_at = ld_dev(&C->pause_at);  // (read once: every workgroup decides alike)
   }
   // (the launch's first round number is read back at its end: nothing else writes it, and a
   // register live across the whole launch spilled the PERIODIC big-slab kernel)
@@ -3527,21 +3633,7 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
     const uint32_t p = r % 3;
     if (w == wbk) {
       if (rs.pend) rb_bookkeep(S, rs.pend_ws, rs.pend_we, rs.pend_nb1, rs.pend_new);
-      // reset buffer (r + 1) % 3 for the next round
-      const uint32_t q = (r + 1) % 3;
-      for (uint32_t i = threadIdx.x; i < nch; i += 64) {
-        st_dev(&SK(rb_min)[((size_t)q * RB_CH + i) * RbLayout<kApp>::MS], (uint64_t)INVALID);
-        st_dev(&SK(rb_min)[((size_t)q * RB_CH + i) * RbLayout<kApp>::MS + 1], (uint64_t)INVALID);
-        st_dev(&SK(rb_occ)[((size_t)q * RB_CH + i) * RbLayout<kApp>::OS], (uint64_t)0);
-      }
-      for (uint32_t i = threadIdx.x; i <= nch; i += 64)  // the grid's chunks, then the top counter
-        st_dev(&SK(rb_cnt)[(size_t)q * RbLayout<kApp>::CB + (i == nch ? RB_CH : i) * RbLayout<kApp>::CS], 0u);
-      if (threadIdx.x == 0) {
-        st_dev(&SK(rb_keep)[q], (uint64_t)INVALID);
-        st_dev(&SK(rb_free)[q], (uint64_t)0);
-        st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + q], (uint64_t)0);
-        st_dev(&SK(rb_occ)[3 * RB_CH * RB_OS_MAX + 3 + q], (uint64_t)0);
-      }
+      rb_reset<kApp, false>(S, (r + 1) % 3, nch);  // for the next round
     }
     // diagnostics (SGN_STAMPS): per round of this launch, {earliest start, latest arrival,
     // round edge known} on the 100 MHz clock
@@ -3549,14 +3641,7 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
     if (rd && threadIdx.x == 0)
       __hip_atomic_fetch_min(rd, (unsigned long long)__builtin_amdgcn_s_memrealtime(),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x == 0) {
-      X.ob->keepmin = &SK(rb_keep)[p];
-      X.ob->bbase = ws;
-      X.ob->pg_avail = rs.pg_avail;
-      X.ob->pg_freed = &SK(rb_free)[p];
-      X.ob->pg_allocd = &SK(rb_occ)[3 * RB_CH * RB_OS_MAX + p];
-      X.ob->spilled = &SK(rb_occ)[3 * RB_CH * RB_OS_MAX + 3 + p];
-    }
+    if (threadIdx.x == 0) ob_round_begin(S, X, p, ws, rs.pg_avail);
     uint64_t kall = INVALID, mall = INVALID, oall = 0;
     bool arrived = false;
     for (uint32_t g = gq0; g < gq1; g += gqs) {
@@ -3598,46 +3683,12 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
     asm volatile("" ::: "memory");
     const RbEdge e = rb_edge<kApp>(S, p, nch, ws, we);
     if (rd && w == wbk && threadIdx.x == 0) st_dev(rd + 2, (uint64_t)__builtin_amdgcn_s_memrealtime());
-    // This round's bucket bookkeeping (consumed minima -> INVALID, bucket b1 -> nb1) is done by
-    // workgroup 0 during the next round, with plain stores: safe while the next round's sends
-    // cannot reach this round's buckets. They can after an idle gap: a send at t maps to this
-    // round's bucket indices again once t >= bucketstart(ws) + NB * BW, and t < we' + max_lat.
-    // Then (every workgroup decides alike) workgroup 0 does it now and a second grid barrier
-    // keeps every send of the next round behind it (a lost bucket minimum).
-    const uint64_t span = (uint64_t)SK(NB) * SK(BW);
-    const uint64_t bstart = SIM_START + SK(bw_div).div(ws - SIM_START) * SK(BW);
-    const bool gap = e.active && (e.we + SK(max_lat) >= bstart + span || e.we + SK(max_lat) < e.we);
-    if (gap) {
-      if (w == wbk) rb_bookkeep(S, ws, we, e.nb1, ks);  // (the previous round's: done at this round's start)
-      if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // workgroup 0's stores are done
-        SGN_GLB uint32_t* gc = SK(rb_cnt) + 3 * RB_CB_MAX;
-        const uint32_t target = (rs.ngap + 1) * P;
-        __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t sp = 0;
-        while (ld_dev(gc) < target && ++sp < (1u << 24)) __builtin_amdgcn_s_sleep(2);
-        if (sp >= (1u << 24)) fail_timeout(sk_mem(S));
-        rs.ngap++;
-      }
-    }
+    const bool gap =
+        gap_barrier(S, rs, w == wbk, P, ws, we, ks, e.active, e.we, e.nb1, [&] { fail_timeout(sk_mem(S)); });
     __syncthreads();
     if (threadIdx.x == 0) {
-      // the spare slab set (survivors + this round's new runs for b1) becomes bucket b1
-      const uint32_t b1 = bucket_of(S, we - 1);
-      const uint32_t slab_b1 = lds_tab ? X.lbs[b1] : ld_dev(&SK(bucket_slab)[b1]);
-      if (lds_tab) X.lbs[b1] = (uint16_t)ks;
-      rs.pend = gap ? 0u : 1u;
-      rs.pend_ws = ws;
-      rs.pend_we = we;
-      rs.pend_nb1 = e.nb1;
-      rs.pend_new = ks;
-      rs.ks = slab_b1;
-      rs.ws = e.ws;
-      rs.we = e.we;
-      rs.active = e.active;
-      rs.pg_avail += e.nfree;  // this round's freed pages (all written: barrier)
-      rs.pg_alloc += e.nalloc;
-      rs.occ += e.occd;
+      round_state_advance(S, X, rs, lds_tab, bucket_of(S, we - 1), ws, we, ks, gap, e.nb1, e.ws, e.we, e.active,
+                          e.nfree, e.nalloc, e.occd);
       rs.nspill += e.nspill;
       if (e.active) {  // the next round's guards: every workgroup decides alike (same values)
         const uint64_t need = codel_round_bound(S, rs.occ, e.ws, e.we);
@@ -3652,33 +3703,11 @@ __device__ __forceinline__ void rounds_body(const DevSim* __restrict__ Sg, uint3
     }
     __syncthreads();
   }
-  // the launch's per-wave statistics, in the slot of this workgroup's first group (the host sums
-  // the slots; the mapping is a bijection, so gq0 < G is this workgroup's alone — a forced grid
-  // larger than G has workgroups w >= G; one without groups has nothing to flush)
-  __syncthreads();
-  if (X.wacc && threadIdx.x < W_N && X.wacc[threadIdx.x] && gq0 < gq1) {
-    const uint32_t k = threadIdx.x;
-    if (k == W_MAXFILL)
-      __hip_atomic_fetch_max(&SK(w_cnt)[k * SK(G) + gq0], X.wacc[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-      cnt_add(&SK(w_cnt)[k * SK(G) + gq0], X.wacc[k]);
-  }
+  wacc_flush(S, X, gq0, gq1);
   // the last round's bookkeeping and the host-visible control block
   if (w == wbk) {
     if (rs.pend) rb_bookkeep(S, rs.pend_ws, rs.pend_we, rs.pend_nb1, rs.pend_new);
-    if (threadIdx.x == 0) {
-      st_dev(&C->keep_slab, rs.ks);
-      st_dev(&C->ws, rs.ws);
-      st_dev(&C->we, rs.we);
-      st_dev(&C->active, rs.active);
-      st_dev(&C->rounds, ld_dev(&C->rounds) + r);
-      st_dev(&C->pg_avail, rs.pg_avail);
-      st_dev(&C->cal_occ, rs.occ);
-      if (rs.hold) {
-        st_dev(&C->hold, rs.hold);
-        st_dev(&C->hold_need, rs.hold_need);
-      }
-    }
+    if (threadIdx.x == 0) round_state_store(C, rs, ld_dev(&C->rounds) + r, nullptr);
     // ... and its copy in host memory: after the last barrier no other workgroup writes the
     // control block (their counters and flags arrived with them)
     if (SK(ctrl_mirror)) {
@@ -3709,7 +3738,11 @@ __global__ __launch_bounds__(64, 2) void k_rounds_diag(const DevSim* __restrict_
 // ---- persistent multi-shard rounds (k_rounds_x) ----
 // N shards, each on its own GPU (one launch per GPU) or, for the one-GPU rehearsal, on its own
 // range of workgroups of ONE launch. A round of shard s is the single-shard persistent round
-// (k_rounds) plus the exchange that replaces the RCCL send/recv and k_import:
+// (k_rounds) plus the exchange that replaces the RCCL send/recv and k_import — in the source too:
+// both kernels call the shared round steps above (wg_groups, rb_reset0 / rb_reset,
+// round_state_load, ob_round_begin, gap_barrier, round_state_advance, wacc_flush,
+// round_state_store) and the local round edge (rb_edge, rb_bookkeep); what is written here only is
+// the exchange (the arrival that learns it is last, the messages, the imports: file_run):
 //  1. execute: runs for another shard's hosts go straight into that shard's inbox slot for this
 //     shard and round parity (peer-mapped memory, system-scope write-through stores), counted
 //     per peer in local counters (Worker::send_packet pushes into the destination host's queue
@@ -3827,6 +3860,29 @@ __device__ __forceinline__ u64x2 ld_gran16(SGN_GLB const uint64_t* p, bool sys) 
   return v;
 }
 
+// A run another shard sent, for group g, into the calendar with the workgroup's bucket -> slab
+// table as it is now: a run at or past the horizon fhz is an overflow (OVF_HORIZON); the bucket
+// minimum except in the sbn buckets from sb0 (the window the run will be gathered in). Returns
+// whether the run went past its slab: into the extension, or the spill area — the gathers read it
+// there, and the spill flag holds the round after on every shard for the re-layout.
+__device__ __forceinline__ bool file_run(const DevSim& S, const ExecLDS& X, SGN_GLB Ctrl* C, const EvRec& ev,
+                                         uint32_t g, uint64_t fhz, uint32_t sb0, uint32_t sbn) {
+  if (ev.time >= fhz) {
+    if ((atomicOr(&C->overflow, OVF_HORIZON) & OVF_HORIZON) == 0) C->overflow_info = ev.dst;
+    return false;
+  }
+  const uint32_t b = bucket_of(S, ev.time);
+  const size_t idx = (size_t)X.lbs[b] * S.G + g;
+  const uint32_t pos = atomicAdd(&S.slab_n[idx], 1u);
+  if (((b - sb0) & (S.NB - 1)) >= sbn) min_nr(&S.bucket_min[b], ev.time);
+  if (pos < S.CAP) {
+    st_dev_rec(S.pool + idx * S.CAP + pos, ev);
+    return false;
+  }
+  place_overflow(S, nullptr, (uint32_t)idx, pos, ev);
+  return true;
+}
+
 template <uint32_t kApp>
 __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ L, uint32_t max_rounds) {
   // this workgroup's shard and its place in the shard's range
@@ -3843,16 +3899,8 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
     if (threadIdx.x < W_N) wacc_[threadIdx.x] = 0;
   }
   // the workgroup's groups, as in k_rounds
-  uint32_t gq0_i = w_i, gq1_i = S.G, gqs_i = P_i;
-  if constexpr (kApp == SGN_TRAFFIC_PERIODIC) {
-    const uint32_t x = w_i & 7u, cx = (P_i - x + 7u) >> 3;
-    uint32_t before = 0;
-    for (uint32_t y = 0; y < x; y++) before += (P_i - y + 7u) >> 3;
-    const uint32_t s0 = (uint32_t)((uint64_t)S.G * before / P_i), s1 = (uint32_t)((uint64_t)S.G * (before + cx) / P_i);
-    gq0_i = s0 + (w_i >> 3);
-    gq1_i = s1;
-    gqs_i = cx;
-  }
+  uint32_t gq0_i, gq1_i, gqs_i;
+  wg_groups<kApp>(S.G, w_i, P_i, gq0_i, gq1_i, gqs_i);
   const uint32_t w = w_i, P = P_i, gq0 = gq0_i, gq1 = gq1_i, gqs = gqs_i;
   const uint32_t R = S.n_ranks, me = S.rank;
   const uint32_t nch = (P + 63) >> 6;
@@ -3864,7 +3912,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
     __shared__ uint32_t verdict;
     SGN_GLB Ctrl* C0 = L->S[0]->ctrl;
     const uint32_t ep32 = (uint32_t)L->epoch << 2;
-    if (w == P - 1 && !L->refuse) rb_reset0<kApp>(S, (P + 63) >> 6);
+    if (w == P - 1 && !L->refuse) rb_reset0<kApp, true>(S, (P + 63) >> 6);
     if (threadIdx.x == 0) {
       bool decided = true;
       // (a refused launch is one workgroup on a GPU that cannot hold the grid: it only tells the
@@ -3935,18 +3983,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
   };
   __shared__ RoundLDS rs;
   if (threadIdx.x == 0) {
-    rs.pg_avail = ld_dev(&C->pg_avail);
-    rs.ws = ld_dev(&C->ws);
-    rs.we = ld_dev(&C->we);
-    rs.active = (uint16_t)ld_dev(&C->active);
-    rs.ks = ld_dev(&C->keep_slab);
-    rs.pend = 0;
-    rs.ngap = 0;
-    rs.pg_alloc = ld_dev(&C->pg_alloc);
-    rs.occ = ld_dev(&C->cal_occ);
-    rs.hold = ld_dev(&C->hold);
-    rs.hold_need = ld_dev(&C->hold_need);
-    rs.pause_at = ld_dev(&C->pause_at);  // (read once; the host writes every shard the same target)
+    round_state_load(rs, C);
     rs.fpend = 0;
     rs.n_in = 0;
     rs.last = 0;
@@ -3983,19 +4020,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
       const EvRec ev = S.xsys ? ld_sys_rec(src) : ld_dev_rec(src);
       const uint32_t g = (ev.dst - S.lo) >> S.gsh;
       if (own && (g < gq0 || g >= gq1 || (g - gq0) % gqs != 0)) continue;
-      if (ev.time >= fhz) {
-        if ((atomicOr(&C->overflow, OVF_HORIZON) & OVF_HORIZON) == 0) C->overflow_info = ev.dst;
-        continue;
-      }
-      const uint32_t b = bucket_of(S, ev.time);
-      const size_t idx = (size_t)X.lbs[b] * S.G + g;
-      const uint32_t pos = atomicAdd(&S.slab_n[idx], 1u);
-      if (((b - sb0) & (S.NB - 1)) >= sbn) min_nr(&S.bucket_min[b], ev.time);
-      if (pos < S.CAP)
-        st_dev_rec(S.pool + idx * S.CAP + pos, ev);
-      else  // the extension, or the spill area: the gathers read it there, and the spill flag
-            // holds the round after on every shard for the re-layout
-        place_overflow(S, nullptr, (uint32_t)idx, pos, ev);
+      (void)file_run(S, X, C, ev, g, fhz, sb0, sbn);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
@@ -4010,39 +4035,13 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
     const uint32_t p = r % 3;
     if (w == wbk) {
       if (rs.pend) rb_bookkeep(S, rs.pend_ws, rs.pend_we, rs.pend_nb1, rs.pend_new);
-      // reset buffer (r + 1) % 3 for the next round: minima, counters, both barriers, exports
-      const uint32_t q = (r + 1) % 3;
-      for (uint32_t i = threadIdx.x; i < nch; i += 64) {
-        st_dev(&S.rb_min[((size_t)q * RB_CH + i) * RbLayout<kApp>::MS], (uint64_t)INVALID);
-        st_dev(&S.rb_min[((size_t)q * RB_CH + i) * RbLayout<kApp>::MS + 1], (uint64_t)INVALID);
-        st_dev(&S.rb_occ[((size_t)q * RB_CH + i) * RbLayout<kApp>::OS], (uint64_t)0);
-      }
-      for (uint32_t i = threadIdx.x; i <= nch; i += 64) {
-        const size_t o = (size_t)q * RbLayout<kApp>::CB + (i == nch ? RB_CH : i) * RbLayout<kApp>::CS;
-        st_dev(&S.rb_cnt[o], 0u);
-        st_dev(&S.rb2_cnt[o], 0u);
-      }
-      for (uint32_t i = threadIdx.x; i < R; i += 64) {
-        st_dev(&S.xout_n[q * R + i], 0u);
-        st_dev(&S.xout_n[(3 + q) * R + i], 0u);
-      }
-      if (threadIdx.x == 0) {
-        st_dev(&S.rb_keep[q], (uint64_t)INVALID);
-        st_dev(&S.rb_free[q], (uint64_t)0);
-        st_dev(&S.rb_occ[3 * RB_CH * RB_OS_MAX + q], (uint64_t)0);
-        st_dev(&S.rb_occ[3 * RB_CH * RB_OS_MAX + 3 + q], (uint64_t)0);
-      }
+      rb_reset<kApp, true>(S, (r + 1) % 3, nch);  // for the next round: both barriers and the exports too
     }
     // (the bins this round's gathers read were filled with parity (rounds0 + r) & 1 last round;
     // the next round sends with it again)
     bin_counters_reset((uint32_t)((rounds0 + r) & 1));
     if (threadIdx.x == 0) {
-      X.ob->keepmin = &S.rb_keep[p];
-      X.ob->bbase = ws;
-      X.ob->pg_avail = rs.pg_avail;
-      X.ob->pg_freed = &S.rb_free[p];
-      X.ob->pg_allocd = &S.rb_occ[3 * RB_CH * RB_OS_MAX + p];
-      X.ob->spilled = &S.rb_occ[3 * RB_CH * RB_OS_MAX + 3 + p];
+      ob_round_begin(S, X, p, ws, rs.pg_avail);
       X.ob->xn = S.xout_n + (size_t)p * R;
       X.ob->xc = S.xin_bins ? rs.nin : nullptr;
       X.ob->xbuf = (uint32_t)((rounds0 + r + 1) & 1);
@@ -4231,6 +4230,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
     // Runahead::get (runahead.rs:44-57) over the global min used latency; the controller
     // (controller.rs:88-112) over the global min next event
     const uint64_t min_next = gm;  // (each message's minimum is already unwrapped: EMU_MAX = none)
+    // (window_end's rule written out, as in rb_edge)
     uint64_t ra = (S.dynamic && gmu != INVALID) ? gmu : S.min_possible;
     ra = ra > S.runahead_cfg ? ra : S.runahead_cfg;
     uint64_t ne = min_next + ra;
@@ -4267,41 +4267,16 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
     }
     // the idle-gap case of k_rounds: the bookkeeping now, and a local barrier before any send of
     // the next round can reach this round's bucket indices again
-    const uint64_t span = (uint64_t)S.NB * S.BW;
-    const uint64_t bstart = SIM_START + S.bw_div.div(ws - SIM_START) * S.BW;
-    const bool gap = active && (ne + S.max_lat >= bstart + span || ne + S.max_lat < ne);
-    if (gap) {
-      if (w == wbk) rb_bookkeep(S, ws, we, e_nb1, ks);
-      if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        SGN_GLB uint32_t* gc = S.rb_cnt + 3 * RB_CB_MAX;
-        const uint32_t target = (rs.ngap + 1) * P;
-        __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t sp = 0;
-        while (ld_dev(gc) < target && ++sp < (1u << 24)) __builtin_amdgcn_s_sleep(2);
-        if (sp >= (1u << 24)) atomicOr((unsigned int*)&C->overflow, OVF_TIMEOUT);
-        rs.ngap++;
-      }
-    }
+    // (a barrier that does not complete: the bare flag, as this kernel's other timeouts)
+    const bool gap = gap_barrier(S, rs, w == wbk, P, ws, we, ks, active, ne, e_nb1,
+                                 [&] { atomicOr((unsigned int*)&C->overflow, OVF_TIMEOUT); });
     if (lane < XR_MAX) rs.nin[lane] = nin_l;  // (lanes >= R hold 0)
     __syncthreads();
     const uint32_t b1 = bucket_of(S, we - 1);
     if (threadIdx.x == 0) {
-      // the spare slab set (survivors + this round's new runs for b1) becomes bucket b1
-      const uint32_t slab_b1 = X.lbs[b1];
-      X.lbs[b1] = (uint16_t)ks;
-      rs.pend = gap ? 0u : 1u;
-      rs.pend_ws = ws;
-      rs.pend_we = we;
-      rs.pend_nb1 = e_nb1;
-      rs.pend_new = ks;
-      rs.ks = slab_b1;
-      rs.ws = min_next;
-      rs.we = ne;
-      rs.active = active;
-      rs.pg_avail += e_nfree;
-      rs.pg_alloc += e_nalloc;
-      rs.occ += e_occd + n_in + bin_l;  // (every import counts from here: slots and bins)
+      // (every import counts from here: slots and bins)
+      round_state_advance(S, X, rs, true, b1, ws, we, ks, gap, e_nb1, min_next, ne, active, e_nfree, e_nalloc,
+                          e_occd + n_in + bin_l);
       rs.n_in = n_in;
       rs.hold = hflags;
       rs.hold_need = own_need;
@@ -4363,20 +4338,7 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
         if (ok) {
           SGN_GLB uint64_t* pw = (SGN_GLB uint64_t*)(bp + e0) + 3;
           if (S.xsys) st_sys(pw, 0ull); else st_dev(pw, (uint64_t)0);
-          if (ev.time >= fhz) {
-            if ((atomicOr(&C->overflow, OVF_HORIZON) & OVF_HORIZON) == 0) C->overflow_info = ev.dst;
-          } else {
-            const uint32_t b = bucket_of(S, ev.time);
-            const size_t idx = (size_t)X.lbs[b] * S.G + g;
-            const uint32_t pos = atomicAdd(&S.slab_n[idx], 1u);
-            if (((b - sb0) & (S.NB - 1)) >= sbn) min_nr(&S.bucket_min[b], ev.time);
-            if (pos < S.CAP) {
-              st_dev_rec(S.pool + idx * S.CAP + pos, ev);
-            } else {
-              place_overflow(S, nullptr, (uint32_t)idx, pos, ev);
-              spilled = true;
-            }
-          }
+          if (file_run(S, X, C, ev, g, fhz, sb0, sbn)) spilled = true;
         }
         const uint64_t m = __ballot(ok && e == E - 1);
         if (!m) break;
@@ -4389,31 +4351,11 @@ __global__ __launch_bounds__(64, 2) void k_rounds_x(const XLaunch* __restrict__ 
     if (__ballot(spilled) && threadIdx.x == 0)
       (void)__hip_atomic_fetch_max(&C->spill_imp, ld_dev(&C->spill_n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  // the launch's per-wave statistics (k_rounds)
-  __syncthreads();
-  if (X.wacc && threadIdx.x < W_N && X.wacc[threadIdx.x] && gq0 < gq1) {
-    const uint32_t k = threadIdx.x;
-    if (k == W_MAXFILL)
-      __hip_atomic_fetch_max(&S.w_cnt[k * S.G + gq0], X.wacc[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-      cnt_add(&S.w_cnt[k * S.G + gq0], X.wacc[k]);
-  }
+  wacc_flush(S, X, gq0, gq1);
+  // the last round's bookkeeping and the host-visible control block
   if (w == wbk) {
     if (rs.pend) rb_bookkeep(S, rs.pend_ws, rs.pend_we, rs.pend_nb1, rs.pend_new);
-    if (threadIdx.x == 0) {
-      st_dev(&C->keep_slab, rs.ks);
-      st_dev(&C->ws, rs.ws);
-      st_dev(&C->we, rs.we);
-      st_dev(&C->active, (uint32_t)rs.active);
-      st_dev(&C->rounds, rounds0 + r);
-      st_dev(&C->pg_avail, rs.pg_avail);
-      st_dev(&C->cal_occ, rs.occ);
-      (void)__hip_atomic_fetch_max(&C->spill_imp, X.big->spill_imp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (rs.hold) {
-        st_dev(&C->hold, rs.hold);
-        st_dev(&C->hold_need, rs.hold_need);
-      }
-    }
+    if (threadIdx.x == 0) round_state_store(C, rs, rounds0 + r, &X.big->spill_imp);
   }
 }
 
@@ -4438,12 +4380,8 @@ __device__ __forceinline__ void advance_window(const DevSim& S, Ctrl* C) {
   if (S.dynamic && mu != INVALID && mu < C->min_used) C->min_used = mu;
   const uint64_t min_next = m == INVALID ? EMU_MAX : m;
   C->last_min_next = min_next;
-  // Runahead::get (runahead.rs:44-57)
-  uint64_t ra = (S.dynamic && C->min_used != INVALID) ? C->min_used : S.min_possible;
-  ra = ra > S.runahead_cfg ? ra : S.runahead_cfg;
-  uint64_t ne = min_next + ra;
-  if (ne < min_next || ne > EMU_MAX) ne = EMU_MAX;
-  ne = ne < S.end_time ? ne : S.end_time;
+  const uint64_t ne = window_end(min_next, S.dynamic ? C->min_used : INVALID, S.dynamic, S.min_possible,
+                                 S.runahead_cfg, S.end_time);
   C->active = min_next < ne ? 1u : 0u;
   C->prev_we = C->we;
   C->ws = min_next;

@@ -670,6 +670,48 @@ __host__ __device__ __forceinline__ uint64_t codel_pages_bound(uint64_t due, uin
   return (due + 15 * (due < hosts ? due : hosts) + 15) / 16;
 }
 
+// The next window's end from the minimum next event time: Runahead::get (runahead.rs:44-57: the
+// smallest latency used so far when the runahead is dynamic and one was used — min_used, INVALID =
+// none —, else the smallest possible one, and never below the configured runahead), then
+// Controller::manager_finished_current_round (controller.rs:88-112: clamped to EMU_MAX and to the
+// simulation's end). The window [min_next, end) is active while min_next < end. The rule of every
+// round edge: finalize_fused and advance_window call it; rb_edge and k_rounds_x's exchange keep it
+// written out (engine.hip: through the call the persistent kernels waited for min_used early).
+__host__ __device__ __forceinline__ uint64_t window_end(uint64_t min_next, uint64_t min_used, bool dynamic,
+                                                        uint64_t min_possible, uint64_t runahead_cfg,
+                                                        uint64_t end_time) {
+  uint64_t ra = (dynamic && min_used != INVALID) ? min_used : min_possible;
+  ra = ra > runahead_cfg ? ra : runahead_cfg;
+  uint64_t ne = min_next + ra;
+  if (ne < min_next || ne > EMU_MAX) ne = EMU_MAX;
+  return ne < end_time ? ne : end_time;
+}
+
+// The groups of workgroup w of a persistent grid of P over G groups: [gq0, gq1) in steps of gqs.
+// TGEN: w, w + P, ... (config C's server groups come first in slot order and set the round's
+// chain: dealt over every XCD). PERIODIC: XCD-aware — workgroups are dealt round-robin over the 8
+// XCDs (blockIdx % 8; observed, used for speed only), so the ones sharing w % 8 take one
+// contiguous eighth of the groups. Slots are ordered by graph node (sim_init), so an XCD's hosts
+// cover an eighth of the nodes and their sends read an eighth of the route table's rows (config
+// D: 2 of 16 MB, L2-resident). Any fixed bijection works: a group's records belong to its
+// workgroup for the launch.
+template <uint32_t kApp>
+__host__ __device__ __forceinline__ void wg_groups(uint32_t G, uint32_t w, uint32_t P, uint32_t& gq0,
+                                                   uint32_t& gq1, uint32_t& gqs) {
+  gq0 = w;
+  gq1 = G;
+  gqs = P;
+  if constexpr (kApp == SGN_TRAFFIC_PERIODIC) {
+    const uint32_t x = w & 7u, cx = (P - x + 7u) >> 3;  // this class's workgroups
+    uint32_t before = 0;                                 // workgroups of the classes below x
+    for (uint32_t y = 0; y < x; y++) before += (P - y + 7u) >> 3;
+    const uint32_t s0 = (uint32_t)((uint64_t)G * before / P), s1 = (uint32_t)((uint64_t)G * (before + cx) / P);
+    gq0 = s0 + (w >> 3);
+    gq1 = s1;
+    gqs = cx;
+  }
+}
+
 // persistent rounds (k_rounds, k_rounds_x): the round buffers' sizes (RbLayout in engine.hip)
 constexpr uint32_t RB_CH = 64;  // chunk slots per buffer (persistent grids up to 4096 workgroups)
 constexpr uint32_t RB_CS_MAX = 32, RB_MS_MAX = 16, RB_OS_MAX = 16, RB_CB_MAX = (RB_CH + 1) * RB_CS_MAX;

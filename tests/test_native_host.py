@@ -1,7 +1,9 @@
 """Host-side checks of libsgn's internal arithmetic helpers (CPU only).
 
 sgn::UDiv64 replaces the device's u64 division by the calendar bucket width with a
-multiply-high and shifts; it must equal x / d for every u64 x."""
+multiply-high and shifts; it must equal x / d for every u64 x. The round rules the kernels
+share with host code (sgn::wg_groups, sgn::window_end) are checked through
+tests/native/round_rules_check.cpp."""
 import pathlib
 import subprocess
 
@@ -123,27 +125,47 @@ def test_periodic_round_kernel_lds_budget():
             assert -(-total // 512) * 512 * 8 <= 160 * 1024, (name, m, total)
 
 
-def _periodic_groups(w, P, G):
-    """The PERIODIC persistent kernel's group list for workgroup w of P (k_rounds, engine.hip):
-    the workgroups sharing w % 8 take one contiguous eighth of the G groups."""
-    x = w & 7
-    cx = (P - x + 7) >> 3
-    before = sum((P - y + 7) >> 3 for y in range(x))
-    s0, s1 = G * before // P, G * (before + cx) // P
-    return list(range(s0 + (w >> 3), s1, cx))
+@pytest.fixture(scope="module")
+def round_rules(tmp_path_factory):
+    """tests/native/round_rules_check.cpp, built and run once: its output, and the PERIODIC group
+    lists it prints from sgn::wg_groups (csrc/sgn_internal.h, the kernels' own split) as
+    {(P, G): {w: [groups]}}."""
+    exe = tmp_path_factory.mktemp("round_rules") / "round_rules_check"
+    subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17",
+                    "-I", str(ROOT / "include"), "-I", str(ROOT / "shadow-gen_amd" / "csrc"),
+                    str(ROOT / "tests" / "native" / "round_rules_check.cpp"), "-o", str(exe)],
+                   check=True, capture_output=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    groups = {}
+    for line in out.stdout.splitlines():
+        if line.startswith("groups "):
+            head, _, tail = line.partition(":")
+            _, P, G, w = head.split()
+            groups.setdefault((int(P), int(G)), {})[int(w)] = [int(g) for g in tail.split()]
+    return out, groups
+
+
+def test_round_rules_match_their_restatement(round_rules):
+    """wg_groups for the three traffic kinds (every group exactly once per round; PERIODIC: one
+    contiguous range per w % 8 class) and window_end against a plain restatement."""
+    out, _ = round_rules
+    assert out.returncode == 0, out.stdout[-2000:]
+    assert " 0 bad" in out.stdout.splitlines()[-1]
 
 
 @pytest.mark.parametrize("P,G", [(1, 1), (2, 5), (7, 7), (9, 100), (625, 625), (2048, 15625),
                                  (1792, 15625), (2040, 15625), (300, 200)])
-def test_periodic_xcd_group_mapping_is_a_bijection(P, G):
+def test_periodic_xcd_group_mapping_is_a_bijection(P, G, round_rules):
     # every group exactly once per round, each workgroup's groups inside its XCD class's
     # contiguous range (P > G: the oversized-grid test hook leaves some workgroups idle)
+    groups = round_rules[1][(P, G)]
+    assert sorted(groups) == list(range(P))
     seen = []
     for w in range(P):
-        gs = _periodic_groups(w, P, G)
+        gs = groups[w]
         assert all(0 <= g < G for g in gs)
         seen += gs
     assert sorted(seen) == list(range(G))
     for x in range(min(8, P)):  # one contiguous range per class
-        cls = sorted(g for w in range(x, P, 8) for g in _periodic_groups(w, P, G))
+        cls = sorted(g for w in range(x, P, 8) for g in groups[w])
         assert cls == list(range(cls[0], cls[-1] + 1)) if cls else True

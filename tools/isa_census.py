@@ -22,7 +22,9 @@ a scalar-cache round trip), with a summary per base register:
 
 `--same A.s B.s` answers whether two builds have the same kernels (a refactor of the host code
 must not change one): every function symbol of both listings, its instruction stream compared
-with the comments stripped and the numbers of local labels blanked.
+with the comments stripped and the numbers of local labels blanked. With `--blank-regs` the
+line-table labels, register numbers and spill lanes are ignored too, and a differing pair's places
+are listed: where a refactor of device code moved instructions, and that it moved no others.
 """
 import argparse
 import collections
@@ -232,14 +234,33 @@ def functions(asm_path):
     return out
 
 
-def same(a_path, b_path):
+_REG = re.compile(r"\b([sv])(\d+|\[\d+:\d+\])")
+_SPILL_LANE = re.compile(r"^(v_(?:read|write)lane_b32 .*), \d+$")
+
+
+def _blank(lines):
+    """A stream with the line-table labels dropped and register numbers and SGPR spill lanes
+    blanked: what is left differs only where the instructions themselves do."""
+    return [_REG.sub(lambda k: k.group(1) + "#", _SPILL_LANE.sub(r"\1, #", x)) for x in lines if not x.startswith(".Ltmp_")]
+
+
+def same(a_path, b_path, blank=False):
     """Compare two listings function by function; prints one line each and returns 0 when both
-    hold the same symbols with identical instruction streams."""
+    hold the same symbols with identical instruction streams. blank: compare the blanked streams
+    (_blank) and list where a differing pair parts, as A's line ranges START+LINES_A/LINES_B."""
     a, b = functions(a_path), functions(b_path)
+    if blank:
+        import difflib
+        a, b = {k: _blank(v) for k, v in a.items()}, {k: _blank(v) for k, v in b.items()}
     bad = 0
     for sym in sorted(set(a) | set(b)):
         if sym not in a or sym not in b:
             print(f"ONLY IN {'A' if sym in a else 'B'}  {sym}")
+            bad += 1
+        elif blank and a[sym] != b[sym]:
+            ops = [o for o in difflib.SequenceMatcher(None, a[sym], b[sym], autojunk=False).get_opcodes() if o[0] != "equal"]
+            print(f"DIFFERENT  {sym}: {len(a[sym])} vs {len(b[sym])} lines, {len(ops)} places: "
+                  + " ".join(f"{o[1]}+{o[2] - o[1]}/{o[4] - o[3]}" for o in ops))
             bad += 1
         elif a[sym] != b[sym]:
             first = next((i for i, (x, y) in enumerate(zip(a[sym], b[sym])) if x != y), min(len(a[sym]), len(b[sym])))
@@ -273,9 +294,11 @@ def main():
     ap.add_argument("--smem", action="store_true", help="list the kernel's scalar loads instead of the census")
     ap.add_argument("--same", nargs=2, metavar=("A.s", "B.s"),
                     help="compare two listings function by function (exit status 1 when they differ)")
+    ap.add_argument("--blank-regs", action="store_true",
+                    help="with --same: ignore line-table labels, register numbers and spill lanes; list where streams part")
     a = ap.parse_args()
     if a.same:
-        return same(*a.same)
+        return same(*a.same, blank=a.blank_regs)
     if a.compile:
         compile_asm(a.compile, a.o)
         return 0
