@@ -288,9 +288,15 @@ int sgn_snapshot_save(sgn_ctx* ctx, sgn_snapshot** out);
  * Trace records are append-only: restore sets the record count back and the re-run writes the
  * same records again. Drain records the caller already took with sgn_drain stay the caller's;
  * records still on the device or held at the save come back.
+ * A snapshot saved here keeps no trace records — those up to its save are in the trace buffer — so
+ * one AHEAD of the position (the run was rewound behind it) restores only while they are still
+ * there: the records past the position stay in place until the cursor of sgn_trace_take moves (a
+ * take, or a restore that takes the cursor back), and come back when the run passes the snapshot's
+ * round again. Otherwise SGN_ESTATE, nothing changed; sgn_snapshot_export follows the same rule, and
+ * an imported snapshot carries its records and always restores.
  * Errors: SGN_EINVAL for a null argument or a snapshot that is not this context's; SGN_ESTATE
- * without a simulation or for a snapshot taken before the last sgn_sim_init; SGN_ENOMEM with
- * nothing changed. */
+ * without a simulation, for a snapshot taken before the last sgn_sim_init, or for one whose trace
+ * records left the buffer (above); SGN_ENOMEM with nothing changed. */
 int sgn_snapshot_restore(sgn_ctx* ctx, const sgn_snapshot* snap);
 
 /* Frees one snapshot (a null argument, or a snapshot that is not this context's: no effect). */
@@ -363,8 +369,10 @@ typedef int (*sgn_read_fn)(void* user, void* data, size_t len);
  * snapshot changes. Device sections are digested on the device before they leave and stream
  * through two pinned staging chunks, so host memory stays bounded whatever the snapshot's size.
  * Trace records [b, min(trace count at the save, b + capacity)) are taken from the context's trace
- * buffer (the engine is deterministic: they are still there), b the records sgn_trace_take has
- * handed out, 0 without a take; the header carries b. bytes (may be NULL): the file's length. */
+ * buffer (the engine is deterministic: they are still there — or, for a snapshot ahead of the
+ * position after the cursor moved, SGN_ESTATE as for sgn_snapshot_restore), b the records
+ * sgn_trace_take has handed out, 0 without a take; the header carries b. bytes (may be NULL): the
+ * file's length. */
 int sgn_snapshot_export(sgn_ctx* ctx, const sgn_snapshot* snap, sgn_write_fn write, void* user, uint64_t* bytes);
 
 /* Builds a new snapshot owned by ctx from a stream, as if sgn_snapshot_save had just taken it here

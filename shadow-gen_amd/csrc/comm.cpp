@@ -397,8 +397,14 @@ int sgn_run_local_group(sgn_ctx* const* ctxs, uint32_t n, uint64_t max_rounds, u
           uint64_t msg[4 * XHDR];
           SGN_HIP(A, hipMemcpy(msg, (const void*)(A->S.xout + (size_t)b * blk), sizeof(msg), hipMemcpyDeviceToHost));
           const uint64_t k = std::min<uint64_t>(msg[0], A->xslot);
-          SGN_HIP(B, hipMemcpy((void*)(B->S.xin + (size_t)a * blk), (const void*)(A->S.xout + (size_t)b * blk),
-                               (size_t)(XHDR + k) * sizeof(EvRec), hipMemcpyDefault));
+          // On B's stream, where its k_import follows: a device-to-device hipMemcpy may return
+          // before the copy is done, and the null stream it runs on orders nothing against the
+          // shards' non-blocking streams — k_import then read the previous round's message or
+          // runs now and then (a window one round late, other counters at the end). A's send
+          // blocks are final: its stream was synchronised after k_execute.
+          SGN_HIP(B, hipSetDevice(B->device));
+          SGN_HIP(B, hipMemcpyAsync((void*)(B->S.xin + (size_t)a * blk), (const void*)(A->S.xout + (size_t)b * blk),
+                                    (size_t)(XHDR + k) * sizeof(EvRec), hipMemcpyDefault, B->stream));
         }
       }
       for (uint32_t i = 0; i < n; i++) {

@@ -788,6 +788,12 @@ struct sgn_ctx {
   // kernels' view is DevSim::trace = trace_buf - trace_base, DevSim::trace_cap = trace_base + trace_cap
   sgn_trace_rec* trace_buf = nullptr;
   uint64_t trace_base = 0;
+  // The records the buffer holds in place, [trace_base, max(trace_held, Ctrl::trace_n)): a rewind
+  // sets trace_n back and leaves the records past it where they are (the re-run writes the same ones
+  // again), so a snapshot AHEAD of the position still finds its records [trace_base, N) there — until
+  // the cursor moves (a take, a restore that takes it back, an imported snapshot's records): what
+  // lay past the position is gone then, and trace_held says so (trace_view_set)
+  uint64_t trace_held = 0;
   std::vector<uint32_t> trace_hosts;      // sgn_trace_hosts (empty: every host is traced)
   void* take_mem = nullptr;               // sgn_trace_take's scratch (staging records, per-host words)
   size_t take_bytes = 0;

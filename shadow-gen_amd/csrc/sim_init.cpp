@@ -152,6 +152,7 @@ void free_sim(sgn_ctx* ctx) {
   ctx->take_bytes = 0;
   ctx->trace_buf = nullptr;  // (in allocs)
   ctx->trace_base = 0;
+  ctx->trace_held = 0;
   for (void* p : ctx->allocs) hipFree(p);
   ctx->allocs.clear();
   ctx->sim_bytes = 0;
@@ -523,6 +524,7 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
     ctx->trace_buf = dalloc<sgn_trace_rec>(ctx, ctx->trace_cap);
     if (!ctx->trace_buf) return set_error(ctx, SGN_ENOMEM, "device allocation failed (trace)");
     ctx->trace_base = 0;  // (nothing taken: the kernels' view is the buffer itself)
+    ctx->trace_held = 0;
     S.trace = (decltype(S.trace))ctx->trace_buf;
     S.trace_cap = ctx->trace_cap;
   }

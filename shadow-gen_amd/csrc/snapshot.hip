@@ -410,6 +410,19 @@ int sgn::snap_check(sgn_ctx* ctx, const sgn_snapshot* snap, const char* what, sg
   if (s->gen != ctx->sim_gen)
     return set_error(ctx, SGN_ESTATE, w + ": the snapshot was taken before the last sgn_sim_init");
   if (!ctx->failed.empty()) return set_error(ctx, SGN_ESTATE, "simulation unusable: " + ctx->failed);
+  // A snapshot saved here keeps no trace records: the records [trace_base, N) it stands for are in
+  // the trace buffer. For a snapshot ahead of the position (N past the live count: the run was
+  // rewound since) that holds only while the cursor has not moved since they were written.
+  if (ctx->trace_buf && !s->imported && s->ctrl.trace_n > ctx->trace_base) {
+    uint64_t live = 0;
+    SGN_HIP(ctx, hipSetDevice(ctx->device));
+    SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SGN_HIP(ctx, hipMemcpy(&live, (const char*)ctx->S.ctrl + offsetof(Ctrl, trace_n), 8, hipMemcpyDeviceToHost));
+    if (s->ctrl.trace_n > std::max(live, ctx->trace_held))
+      return set_error(ctx, SGN_ESTATE, w + ": the trace records up to this snapshot are no longer in the trace buffer (the "
+                                            "run was rewound and the cursor moved since: a take, or a restore of an earlier "
+                                            "snapshot); run forward past its round, or import it from a file");
+  }
   *s_out = s;
   return 0;
 }
@@ -545,6 +558,7 @@ int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
   // a take since the save moved the cursor past N — then it goes back to N, and the re-run
   // produces the records from N on again (they are taken again, like drain records already taken).
   if (ctx->trace_buf) {
+    ctx->trace_held = std::max(ctx->trace_held, live.trace_n);  // (the records past N stay in place)
     uint64_t base = std::min<uint64_t>(ctx->trace_base, s->ctrl.trace_n);
     if (s->trace.bytes) {
       ok = ok && s->trace.bytes <= ctx->trace_cap * sizeof(sgn_trace_rec) && d2d((void*)ctx->trace_buf, s->trace);
@@ -553,6 +567,7 @@ int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
       base = s->trace_b;  // (a file without records: everything up to N was taken before its export)
     }
     if (ok && base != ctx->trace_base) ok = trace_view_set(ctx, base) == 0;
+    if (s->imported) ctx->trace_held = s->ctrl.trace_n;  // (the buffer starts with the file's records now)
   } else {
     ok = ok && s->trace.bytes == 0;
   }

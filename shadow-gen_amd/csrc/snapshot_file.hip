@@ -362,7 +362,8 @@ int export_one(sgn_ctx* ctx, sgn_snapshot* s, sgn_write_fn wr, void* user, uint6
   // the trace records up to the save that sgn_trace_take has not handed out, [b, N): an imported
   // snapshot's own, else the context's — record p is at trace_buf[p - trace_base], so they start
   // the buffer (b = trace_base) or there are none (a take since the save passed N: b = N). Without
-  // a take b = 0 and the section is the records [0, N), as before the call existed.
+  // a take b = 0 and the section is the records [0, N), as before the call existed. (snap_check has
+  // refused a snapshot ahead of the position whose records the buffer no longer holds.)
   const uint64_t trace_b = s->imported ? s->trace_b : std::min<uint64_t>(ctx->trace_base, s->ctrl.trace_n);
   const uint64_t n_trace = s->imported ? s->trace.bytes / sizeof(sgn_trace_rec)
                                        : (ctx->trace_buf ? std::min<uint64_t>(s->ctrl.trace_n - trace_b, ctx->trace_cap) : 0);

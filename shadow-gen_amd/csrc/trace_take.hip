@@ -292,6 +292,7 @@ static_assert(offsetof(DevSim, trace_cap) == offsetof(DevSim, trace) + 8, "trace
 int trace_view_set(sgn_ctx* ctx, uint64_t base) {
   DevSim& S = ctx->S;
   ctx->trace_base = base;
+  ctx->trace_held = base;  // (records past the position were laid out for the old cursor)
   // (unsigned arithmetic: the kernel adds pos * sizeof(record) back, pos >= base)
   S.trace = (decltype(S.trace))((uintptr_t)ctx->trace_buf - (uintptr_t)(base * sizeof(sgn_trace_rec)));
   S.trace_cap = base + ctx->trace_cap;

@@ -179,7 +179,7 @@ def test_apsp_loss_forms_agree(ctxf, oracle, monkeypatch):
 def test_apsp_dense_sweep_form(ctxf, oracle, monkeypatch):
     """The dense form of the loss sweep (loss_sweep_dense: a lane per head, the S sources'
     d[s][v] in registers, -d[s][u] by scalar loads, negated latency and arc-index matrices; the
-    sources' own out-arcs by loss_self_tails) and its fused form (the sweep on the direct arcs
+    sources' own out-arcs in a step of their own inside loss_sweep_dense) and its fused form (the sweep on the direct arcs
     before the squaring, as its first pass: complete graphs) against the oracle, against the
     unfused dense sweep (SGN_APSP_FUSED=0) and against the CSR sweep (SGN_APSP_DENSE=0):
     - Tor graphs: complete, every arc its own shortest path — fused, nothing to shorten;

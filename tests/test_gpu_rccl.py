@@ -67,8 +67,9 @@ def test_xpeer_two_processes_one_gpu_persistent(workload, port, launcher):
     """The N-GPU persistent path itself (k_rounds_x with peer-mapped inboxes): two processes on
     device 0 (SGN_XPEER_SHARED=1 lets the IPC mapping accept a peer on the same GPU; each grid
     is sized for half the GPU), every round's runs stored straight into the other process's
-    inbox bins and slots, the messages (tagged 8-byte words, system-scope release and acquire)
-    and the residency census across processes — against the unsharded run, bit for bit.
+    inbox bins and slots, the messages (tagged 8-byte words behind a system-scope release; the
+    system-scope acquire is off unless the library is built with SGN_XACQ, the tags and inboxes being
+    read by system-coherent loads) and the residency census across processes — against the unsharded run, bit for bit.
     Config C runs as the driver invokes the scaling bench without a launcher: `bench.py --gpus 2`
     starts its two ranks itself and the line says n_gpus 2."""
     env = dict(os.environ, SGN_GRAPH="0", NCCL_DEBUG="WARN", TMPDIR="/tmp", SGN_XPEER_SHARED="1")

@@ -260,6 +260,54 @@ def test_take_rewind(ctxf, periodic):
     assert_same_run(o, c, args[2].n, trace=False)
 
 
+def test_take_snapshot_ahead_of_a_moved_cursor(ctxf, periodic, tmp_path):
+    """A snapshot saved here keeps no records: the records [cursor, N) it stands for are in the
+    buffer. Rewound behind it, they stay in place, and it restores with them pending — until the
+    cursor moves: a take after the rewind starts the buffer anew, and what the buffer then holds at
+    [cursor, N) is not those records (a restore used to hand them out as pending all the same, an
+    export to write them: run-control sweep case 31 ends on such a restore). Both are refused, nothing
+    changes; once the run has passed the snapshot's round again the records are there."""
+    args, o, t = periodic
+    c = make(ctxf, args, 1 << 20, SET6)
+    c.run(100)
+    n100 = c.trace_pending()
+    sa = c.snapshot_save()
+    c.run(100)
+    n200 = c.trace_pending()
+    sb = c.snapshot_save()
+    assert n200 > n100 > 0
+    c.snapshot_restore(sa)  # rewound, the cursor where it was: b's records are still in place
+    assert c.trace_pending() == n100
+    c.snapshot_restore(sb)
+    assert c.trace_pending() == n200 and c.stats()["rounds"] == 200
+    c.snapshot_restore(sa)
+    first, sp = c.trace_take()  # the cursor moves to n100: the buffer starts anew
+    check_take(first, sp, SET6)
+    assert len(first) == n100
+    path = tmp_path / "ahead.snap"
+    for call in (lambda: c.snapshot_restore(sb), lambda: c.snapshot_export(sb, path)):
+        with pytest.raises(sgn.SgnError, match="no longer in the trace buffer") as e:
+            call()
+        assert e.value.rc == ESTATE
+    assert c.stats()["rounds"] == 100 and c.trace_pending() == 0 and not path.exists()
+    c.run(150)  # past b's round: its records are produced again
+    c.snapshot_restore(sb)
+    assert c.stats()["rounds"] == 200 and c.trace_pending() == n200 - n100
+    c.snapshot_export(sb, path)
+    assert sgn.snapshot_file_info(path)["trace_records"] == n200 - n100
+    mid, sm = c.trace_take()
+    check_take(mid, sm, SET6)
+    c.snapshot_restore(c.snapshot_import(path))  # the file's records [n100, n200) are pending again
+    assert c.trace_pending() == n200 - n100
+    again, sg = c.trace_take()
+    same_records(again, mid, "the file's records")
+    c.run()
+    rest, sr = c.trace_take()
+    check_take(rest, sr, SET6)
+    same_records(srt(np.concatenate([first, mid, rest])), only(t, SET6), "every record once")
+    assert_same_run(o, c, args[2].n, trace=False)
+
+
 def _export(c, path):
     s = c.snapshot_save()
     c.snapshot_export(s, path)
