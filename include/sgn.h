@@ -534,6 +534,78 @@ typedef struct sgn_trace_take_timing {
 } sgn_trace_take_timing;
 int sgn_trace_take_timing_get(sgn_ctx* ctx, sgn_trace_take_timing* out);
 
+/* ---- additions to ABI 10 (new calls only; no struct of ABI 10 changes): interval statistics —
+ * what every owned host sent, received and dropped between two samples, read on the device. The
+ * reference has no such output (its only network-level output is the per-host capture above); a
+ * caller that wanted it had to read sgn_host_digests and sgn_stats_get at every pause, which copy
+ * every host record to the CPU. A sample compares the seven per-host counters behind those two
+ * calls with a device-resident baseline and keeps one row per host that changed. The sampler
+ * stands beside the simulation: it reads the counters at a launch boundary and never changes
+ * window, counters, digests or any snapshot. ---- */
+
+typedef struct sgn_sample_row {   /* 64 B: one host's activity between two samples */
+  uint32_t host;                  /* HostId */
+  uint32_t sample;                /* index of the sample that closed the interval (its low 32 bits) */
+  uint64_t sent, popped, delivered, codel_dropped,   /* deltas of the counters behind sgn_host_digest */
+           unknown_dst, local_delivered, blocked;    /* ... and behind sgn_stats' per-host sums */
+} sgn_sample_row;
+
+typedef struct sgn_sample_info {  /* one per sample */
+  uint64_t sample, rounds, window_start, window_end; /* the round edge it was taken at (sgn_window) */
+  uint64_t first_row, rows;       /* its rows inside a take: out[first_row .. first_row + rows) */
+  uint64_t total[7];              /* sum of its rows' seven deltas (the rows' field order), folded on
+                                     the device */
+} sgn_sample_info;
+
+/* After sgn_sim_init, between calls: allocates a device buffer of row_capacity rows and a device
+ * baseline of seven u64 per owned host, set to the counters as they are now. The sample index
+ * starts at 0. A second call re-allocates and rebases: pending rows and samples are dropped and
+ * the index starts at 0 again. A new sgn_sim_init drops the sampler. row_capacity == 0 is
+ * SGN_EINVAL; SGN_ENOMEM leaves the context without a sampler. */
+int sgn_sample_enable(sgn_ctx* ctx, uint64_t row_capacity);
+
+/* Between calls, at whatever round edge the context is at (typically after sgn_run_until); no
+ * held round is resolved, the per-host counters are final at every launch boundary. For every
+ * owned host with any of the seven counters differing from the baseline it appends one row
+ * (current - baseline) to the device row buffer, rows ascending by HostId, sets that host's
+ * baseline to the current values, and records the sample's info (*out, when given, is that info
+ * with first_row = the rows pending before the call). Hosts without a change produce no row; a
+ * sample without rows is still a sample (rows = 0, the index advances).
+ * All or nothing: with fewer free rows than the sample needs, SGN_EOVERFLOW (the message says how
+ * many it needs and how many are free), nothing is appended, baseline and index are unchanged,
+ * and the same call succeeds after a sgn_sample_take.
+ * Works on any context — members of a local group and ranks with a communicator included: it
+ * samples the hosts the context owns and is not a collective.
+ * Rewinds: the sampler is not part of a snapshot and sgn_snapshot_restore /
+ * sgn_shards_snapshot_restore leave it alone. When the context's round count is below the round
+ * count of the baseline (the deltas would be negative) the call returns SGN_ESTATE and nothing
+ * changes; it keeps returning SGN_ESTATE until sgn_sample_rebase. */
+int sgn_sample(sgn_ctx* ctx, sgn_sample_info* out /* may be NULL */);
+
+/* Sets the baseline to the current counters. Emits nothing; pending rows, pending samples and the
+ * sample index stay as they are. */
+int sgn_sample_rebase(sgn_ctx* ctx);
+
+/* Rows and samples appended and not yet taken (either pointer may be NULL). */
+int sgn_sample_pending(sgn_ctx* ctx, uint64_t* rows, uint64_t* samples);
+
+/* Like sgn_trace_take: moves every pending row (ordered by sample, then host) out in one
+ * device-to-host copy, the pending samples' infos with them, and empties the buffer. With cap
+ * below the pending rows or info_cap below the pending samples, SGN_ERANGE, *n_out and *n_infos
+ * say what is needed and nothing is taken. infos may be NULL (info_cap 0) only when no sample is
+ * pending; n_infos may be NULL. */
+int sgn_sample_take(sgn_ctx* ctx, sgn_sample_row* out, uint64_t cap, uint64_t* n_out,
+                    sgn_sample_info* infos, uint64_t info_cap, uint64_t* n_infos);
+
+/* What the context's last sgn_sample spent (measurements; tools/sample_timing.py): the wall time
+ * of the call, the HIP-event times of its three kernels (per-wave count of changed hosts, scan,
+ * scatter of rows + baseline update + totals), its owned hosts and rows; copy_ms is the
+ * HIP-event time of the last sgn_sample_take's device-to-host copy of rows (0 before one).
+ * Errors in common for the six calls: a null context SGN_EINVAL; no simulation, or the sampler not
+ * enabled, SGN_ESTATE; a HIP failure SGN_EDEVICE. */
+typedef struct sgn_sample_timing { double total_ms, kernel_ms[3], copy_ms; uint64_t hosts, rows; } sgn_sample_timing;
+int sgn_sample_timing_get(sgn_ctx* ctx, sgn_sample_timing* out);
+
 /* ------------------------------------------------------------------------------------ */
 /* CPU-resident applications (SGN_TRAFFIC_EXTERNAL)                                      */
 /* ------------------------------------------------------------------------------------ */

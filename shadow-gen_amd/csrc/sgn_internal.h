@@ -798,6 +798,21 @@ struct sgn_ctx {
   void* take_mem = nullptr;               // sgn_trace_take's scratch (staging records, per-host words)
   size_t take_bytes = 0;
   sgn_trace_take_timing take_timing{};    // of the last sgn_trace_take
+  // interval statistics (sample.hip): the device row buffer and the rows pending in it, the
+  // baseline (seven u64 per owned host, counter-major, indexed by HostId - lo) with the round count
+  // it was taken at, the scratch of one sample (header, per-wave counts and offsets), the infos of
+  // the pending samples, and the HIP events of the timing. Not part of a snapshot: a restore
+  // leaves all of it alone, and smp_stale says that the context went behind the baseline
+  // (sgn_sample refuses until sgn_sample_rebase). Dropped by sgn_sim_init (sample_release).
+  void* smp_rows = nullptr;
+  uint64_t smp_cap = 0, smp_pending = 0;
+  void* smp_base = nullptr;
+  void* smp_scratch = nullptr;
+  uint64_t smp_index = 0, smp_base_rounds = 0;
+  bool smp_stale = false;
+  std::vector<sgn_sample_info> smp_infos;
+  hipEvent_t smp_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  sgn_sample_timing smp_timing{};         // of the last sgn_sample (copy_ms: of the last sgn_sample_take)
   uint64_t drain_cap = 0;                 // sgn_drain_enable (EXTERNAL traffic)
   std::vector<uint64_t> handles;          // sgn_submit handles by slot (tag & ~SGN_TAG_EXT)
   std::vector<uint32_t> submit_seq;       // per owned host: submissions so far
@@ -995,6 +1010,8 @@ int inject_runs(sgn_ctx* ctx, const std::vector<EvRec>& runs);  // into the cale
 // DevSim::trace / trace_cap from trace_buf, trace_cap and the cursor `base`, on the host and on the
 // device (every caller changes the cursor between launches, with the stream idle)
 int trace_view_set(sgn_ctx* ctx, uint64_t base);
+// ---- sample.hip: the interval sampler's buffers and events (free_sim: a new simulation has none) ----
+void sample_release(sgn_ctx* ctx);
 // records of the context's trace buffer that a reader may copy now: [trace_base, min(n, trace_base
 // + trace_cap)) for a control block that counts n (n below the cursor: none)
 inline uint64_t trace_held(const sgn_ctx* ctx, uint64_t n) {
@@ -1023,6 +1040,7 @@ uint64_t layout_sig_pools();
 uint64_t layout_sig_interop();
 uint64_t layout_sig_snapshot_file();
 uint64_t layout_sig_trace_take();
+uint64_t layout_sig_sample();
 }  // namespace sgn
 
 #define SGN_HIP(ctx, call)                                   \

@@ -150,6 +150,7 @@ void free_sim(sgn_ctx* ctx) {
   if (ctx->take_mem) hipFree(ctx->take_mem);
   ctx->take_mem = nullptr;
   ctx->take_bytes = 0;
+  sample_release(ctx);
   ctx->trace_buf = nullptr;  // (in allocs)
   ctx->trace_base = 0;
   ctx->trace_held = 0;

@@ -136,6 +136,31 @@ class TraceTakeTiming(C.Structure):
                 ("records", C.c_uint64), ("hosts", C.c_uint64)]
 
 
+SAMPLE_FIELDS = ("sent", "popped", "delivered", "codel_dropped", "unknown_dst", "local_delivered", "blocked")
+EOVERFLOW = -75
+
+
+class SampleRow(C.Structure):
+    _fields_ = [("host", C.c_uint32), ("sample", C.c_uint32)] + [(n, C.c_uint64) for n in SAMPLE_FIELDS]
+
+
+class SampleInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("sample", "rounds", "window_start", "window_end", "first_row", "rows")] + \
+               [("total", C.c_uint64 * 7)]
+
+
+class SampleTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_double), ("kernel_ms", C.c_double * 3), ("copy_ms", C.c_double),
+                ("hosts", C.c_uint64), ("rows", C.c_uint64)]
+
+
+SAMPLE_ROW_DTYPE = np.dtype([("host", "<u4"), ("sample", "<u4")] + [(n, "<u8") for n in SAMPLE_FIELDS])
+SAMPLE_INFO_DTYPE = np.dtype([(n, "<u8") for n in ("sample", "rounds", "window_start", "window_end", "first_row", "rows")] +
+                             [("total", "<u8", (7,))])
+assert SAMPLE_ROW_DTYPE.itemsize == C.sizeof(SampleRow) == 64
+assert SAMPLE_INFO_DTYPE.itemsize == C.sizeof(SampleInfo) == 104
+
+
 DIGEST_DTYPE = np.dtype([("tx", "<u8"), ("rx", "<u8"), ("app", "<u8"), ("rng", "<u8", (4,)),
                          ("next_event_id", "<u8"), ("n_sent", "<u8"), ("n_popped", "<u8"),
                          ("n_delivered", "<u8"), ("n_codel_dropped", "<u8")])
@@ -342,6 +367,12 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         "sgn_trace_take": (C.c_int, [vp, C.POINTER(TraceRec), C.c_uint64, u64p, C.POINTER(TraceSpan), C.c_uint64, u64p]),
         "sgn_trace_take_timing_get": (C.c_int, [vp, C.POINTER(TraceTakeTiming)]),
         "sgn_pcap_write_trace": (C.c_int64, [vp, C.POINTER(TraceRec), C.c_uint64, C.c_uint32, u32p, C.c_uint32]),
+        "sgn_sample_enable": (C.c_int, [vp, C.c_uint64]),
+        "sgn_sample": (C.c_int, [vp, C.POINTER(SampleInfo)]),
+        "sgn_sample_rebase": (C.c_int, [vp]),
+        "sgn_sample_pending": (C.c_int, [vp, u64p, u64p]),
+        "sgn_sample_take": (C.c_int, [vp, C.POINTER(SampleRow), C.c_uint64, u64p, C.POINTER(SampleInfo), C.c_uint64, u64p]),
+        "sgn_sample_timing_get": (C.c_int, [vp, C.POINTER(SampleTiming)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -647,6 +678,60 @@ class Context:
         self.check(self.L.sgn_trace_take_timing_get(self.h, C.byref(t)))
         return {"total_ms": t.total_ms, "kernel_ms": list(t.kernel_ms), "copy_ms": t.copy_ms,
                 "records": t.records, "hosts": t.hosts}
+
+    # ---- interval statistics: per-host counter deltas sampled on the device (sgn_sample_*) ----
+    def sample_enable(self, row_capacity):
+        """After sim_init: a device buffer of row_capacity rows and a baseline of the per-host
+        counters as they are now; the sample index starts at 0."""
+        self.check(self.L.sgn_sample_enable(self.h, row_capacity))
+        self.sample_capacity = int(row_capacity)
+
+    def sample(self):
+        """One sample at the round edge the context is at: a row (counters - baseline) for every
+        owned host that changed, ascending by host, appended on the device. Returns the sample's
+        info as a dict (total: the seven sums in SAMPLE_FIELDS order). SgnError with rc EOVERFLOW
+        when the row buffer has too few free rows (nothing changed: sample_take(), then again)."""
+        i = SampleInfo()
+        self.check(self.L.sgn_sample(self.h, C.byref(i)))
+        d = {n: int(getattr(i, n)) for n, _ in i._fields_ if n != "total"}
+        d["total"] = [int(v) for v in i.total]
+        return d
+
+    def sample_rebase(self):
+        """The baseline := the counters as they are now (after a rewind behind it); emits nothing."""
+        self.check(self.L.sgn_sample_rebase(self.h))
+
+    def sample_pending(self):
+        """(rows, samples) appended and not yet taken."""
+        r, s = C.c_uint64(), C.c_uint64()
+        self.check(self.L.sgn_sample_pending(self.h, C.byref(r), C.byref(s)))
+        return r.value, s.value
+
+    def sample_take(self, cap=None, info_cap=None):
+        """(rows, infos) as arrays of SAMPLE_ROW_DTYPE / SAMPLE_INFO_DTYPE: every pending row,
+        ordered by sample, then host, and the pending samples' infos (infos[k]'s rows are
+        rows[first_row : first_row + rows]); the row buffer is empty afterwards. cap / info_cap: the
+        arrays' sizes (default: what is pending); too small raises SgnError with rc ERANGE,
+        .needed = (rows, samples), and takes nothing."""
+        pr, ps = self.sample_pending()
+        cap = pr if cap is None else cap
+        info_cap = ps if info_cap is None else info_cap
+        rows = np.zeros(cap, dtype=SAMPLE_ROW_DTYPE)
+        infos = np.zeros(info_cap, dtype=SAMPLE_INFO_DTYPE)
+        n, ni = C.c_uint64(), C.c_uint64()
+        rc = self.L.sgn_sample_take(self.h, rows.ctypes.data_as(C.POINTER(SampleRow)) if cap else None, cap, C.byref(n),
+                                    infos.ctypes.data_as(C.POINTER(SampleInfo)) if info_cap else None, info_cap, C.byref(ni))
+        if rc != 0:
+            e = SgnError(rc, self.L.sgn_last_error(self.h).decode())
+            e.needed = (n.value, ni.value)
+            raise e
+        return rows[: n.value], infos[: ni.value]
+
+    def sample_timing(self):
+        t = SampleTiming()
+        self.check(self.L.sgn_sample_timing_get(self.h, C.byref(t)))
+        return {"total_ms": t.total_ms, "kernel_ms": list(t.kernel_ms), "copy_ms": t.copy_ms,
+                "hosts": t.hosts, "rows": t.rows}
 
     # ---- CPU-resident applications (TRAFFIC_EXTERNAL) and the host RNG ----
     def drain_enable(self, cap):
@@ -978,6 +1063,83 @@ def run_captured(ctx, capture, step_ns, until=None):
         capture.feed(*ctx.trace_take())
     capture.feed(*ctx.trace_take())  # (records produced before the call, if any)
     return rounds
+
+
+class Samples:
+    """The samples of a run: .infos (SAMPLE_INFO_DTYPE, one per sample, in order) and .rows
+    (SAMPLE_ROW_DTYPE, ordered by sample, then host); infos[k]'s rows are rows[first_row :
+    first_row + rows]. A host that did not change in an interval has no row there."""
+
+    def __init__(self, rows=None, infos=None):
+        self.rows = np.zeros(0, SAMPLE_ROW_DTYPE) if rows is None else np.ascontiguousarray(rows, dtype=SAMPLE_ROW_DTYPE)
+        self.infos = np.zeros(0, SAMPLE_INFO_DTYPE) if infos is None else np.ascontiguousarray(infos, dtype=SAMPLE_INFO_DTYPE)
+        if int(self.infos["rows"].sum()) != len(self.rows):
+            raise ValueError("Samples: the infos' row counts do not add up to the rows")
+
+    @classmethod
+    def from_takes(cls, takes):
+        """One Samples from the (rows, infos) pairs of successive sample_take() calls: first_row
+        counts from the first take's first row."""
+        rows = [np.zeros(0, SAMPLE_ROW_DTYPE)] + [r for r, _ in takes]
+        infos = [np.zeros(0, SAMPLE_INFO_DTYPE)]
+        base = 0
+        for r, i in takes:
+            i = i.copy()
+            i["first_row"] += base
+            infos.append(i)
+            base += len(r)
+        return cls(np.concatenate(rows), np.concatenate(infos))
+
+    def __len__(self):
+        return len(self.infos)
+
+    def dense(self, field, n_hosts):
+        """[samples, n_hosts] u64: the field's delta of every host in every interval (0 where the
+        host has no row)."""
+        out = np.zeros((len(self.infos), n_hosts), dtype=np.uint64)
+        k = np.repeat(np.arange(len(self.infos)), self.infos["rows"].astype(np.int64))
+        out[k, self.rows["host"]] = self.rows[field]
+        return out
+
+    def cumulative(self, field, n_hosts):
+        """[samples, n_hosts] u64: the field's growth since the baseline, at every sample."""
+        return np.cumsum(self.dense(field, n_hosts), axis=0, dtype=np.uint64)
+
+
+def run_sampled(ctx_or_shards, interval_ns, until=None):
+    """Runs a Context — or this process's shards, as shards_run_until takes them — to the end, or
+    until the next window would start at or after `until`, sampling at every multiple of
+    interval_ns of simulated time at which anything was left to run: run_until the next multiple
+    above the window start, then sample() on every context (sample_enable first; its row capacity
+    need only hold a few samples: the rows are taken when they pass half of it, and at the end).
+    Returns the Samples of the context, or a list of them, one per shard."""
+    many = isinstance(ctx_or_shards, (list, tuple))
+    ctxs = list(ctx_or_shards) if many else [ctx_or_shards]
+    takes = [[] for _ in ctxs]
+    while True:
+        ws, _, active = ctxs[0].window()
+        if not active or (until is not None and ws >= until):
+            break
+        t = SIMULATION_START + ((ws - SIMULATION_START) // interval_ns + 1) * interval_ns
+        t = t if until is None else min(t, until)
+        if many:
+            shards_run_until(ctxs, t)
+        else:
+            ctxs[0].run_until(t)
+        for c, tk in zip(ctxs, takes):
+            try:
+                c.sample()
+            except SgnError as e:
+                if e.rc != EOVERFLOW or c.sample_pending()[0] == 0:
+                    raise
+                tk.append(c.sample_take())
+                c.sample()
+            if 2 * c.sample_pending()[0] > c.sample_capacity:
+                tk.append(c.sample_take())
+    for c, tk in zip(ctxs, takes):
+        tk.append(c.sample_take())
+    out = [Samples.from_takes(tk) for tk in takes]
+    return out if many else out[0]
 
 
 def derive_seeds(sim_seed, names, lib=None):
