@@ -606,6 +606,71 @@ int sgn_sample_take(sgn_ctx* ctx, sgn_sample_row* out, uint64_t cap, uint64_t* n
 typedef struct sgn_sample_timing { double total_ms, kernel_ms[3], copy_ms; uint64_t hosts, rows; } sgn_sample_timing;
 int sgn_sample_timing_get(sgn_ctx* ctx, sgn_sample_timing* out);
 
+/* ---- additions to ABI 10 (new calls only; no struct of ABI 10 changes): the backlog report —
+ * what is STANDING in the network at a round edge, per owned host: the packets in its router's
+ * CoDel queue and the age of the queue's head, what waits in its socket send queue behind the
+ * uplink token bucket, and the packets in flight towards it. Traces, captures and samples report
+ * what has flowed; sgn_stats only has the high-water marks max_codel_len and max_pending_events.
+ * The state is on the device and final at every launch boundary (host records, CoDel page pool,
+ * send-queue rings, event calendar); the report reads it there and stands beside the simulation
+ * like sgn_sample: it writes scratch of its own and nothing else. ---- */
+
+#define SGN_BACKLOG_ROUTER_HELD 1u /* relay_inet_in holds one packet taken from the CoDel queue, waiting for tokens */
+#define SGN_BACKLOG_OUT_HELD    2u /* relay_inet_out holds one packet taken from the interface (IF_POP recorded), not yet sent */
+
+typedef struct sgn_backlog_row {          /* 64 B, one per owned host with anything standing */
+  uint32_t host, flags;                   /* HostId; SGN_BACKLOG_* */
+  uint32_t router_packets, send_packets;  /* CoDel queue / socket send queue, the held packets NOT included */
+  uint64_t router_bytes;                  /* CoDel's total_bytes (wire bytes, as CoDelQueue keeps them) */
+  uint64_t send_bytes;                    /* wire bytes of the send queue: payload + sgn_header_bytes(tag) per packet */
+  uint64_t router_oldest;                 /* enqueue time of the CoDel queue's head (EmulatedTime); SGN_EMUTIME_INVALID when empty */
+  uint32_t inflight_packets;              /* packets in the calendar addressed to this host */
+  uint32_t submit_pending;                /* EXTERNAL: submitted datagrams of this host not yet reached (0 otherwise) */
+  uint64_t inflight_earliest, inflight_latest; /* their delivery times; INVALID / 0 when none */
+} sgn_backlog_row;
+
+typedef struct sgn_backlog_info {
+  uint64_t rounds, window_start, window_end;  /* the round edge (sgn_window) */
+  uint64_t hosts, rows;                       /* owned hosts; hosts with a row */
+  uint64_t total[8];  /* router_packets, router_bytes, router_held, send_packets, send_bytes, out_held, inflight_packets, submit_pending */
+  uint64_t max_router_packets;  uint32_t max_router_host, pad0;
+  uint64_t max_sojourn_ns;      uint32_t max_sojourn_host, pad1;  /* window_start - router_oldest, its largest */
+  uint64_t inflight_earliest;   /* min over rows; INVALID when nothing is in flight */
+} sgn_backlog_info;
+
+/* After sgn_sim_init, between calls, at whatever round edge the context is at (typically after
+ * sgn_run_until); on a finished simulation it reports what is left. A host gets a row when it has
+ * a flag, a packet or a byte in either queue, a packet in flight towards it or a submitted datagram
+ * pending (router_oldest and inflight_earliest are SGN_EMUTIME_INVALID for a host without either, so
+ * they alone make no row); rows ascend by HostId. info->total sums the rows' fields (router_held /
+ * out_held: rows with that flag); the maxima are over the hosts with a non-empty CoDel queue, on
+ * equal values the lowest HostId, 0 / host 0 when no queue holds a packet. Totals and maxima are
+ * folded on the device.
+ * out == NULL with cap == 0 asks for the totals only: SGN_OK, info filled, *n_out = the row count,
+ * no row copied. With out != NULL and cap below the row count: SGN_ERANGE, *n_out says what is
+ * needed, info is filled and nothing is written to out.
+ * Read-only: window, counters, digests, traces, drain records, sampler and snapshots are what they
+ * would be without the call. Its scratch is allocated on first use, sized by the owned hosts, and
+ * freed by sgn_destroy or a new sgn_sim_init.
+ * Held rounds. On a single-shard context a round held for a pool, or runs in the calendar's spill
+ * area, are resolved first, exactly as sgn_snapshot_save does; afterwards every pending event is in
+ * a slab or its extension. A member of a local group or a rank with a communicator cannot resolve
+ * a held edge alone: there the call returns SGN_ESTATE with nothing read (the next collective run
+ * or save call resolves it). At a resolved edge it reports the hosts the context owns, like
+ * sgn_sample, and is not a collective; in-flight packets are counted at the shard that owns the
+ * destination (at a launch's end the imports are filed).
+ * Errors: null ctx, n_out or info (or out == NULL with cap != 0) SGN_EINVAL; no simulation
+ * SGN_ESTATE; a HIP failure, or calendar words that point outside the calendar, SGN_EDEVICE. */
+int sgn_backlog(sgn_ctx* ctx, sgn_backlog_row* out, uint64_t cap, uint64_t* n_out, sgn_backlog_info* info);
+
+/* What the context's last sgn_backlog spent (measurements; tools/backlog_timing.py): the wall time
+ * of the call, the HIP-event times of its four kernels (calendar pass, per-wave count of hosts
+ * with a row, scan, scatter of rows + totals), of the device-to-host copy of the rows (0 for the
+ * totals-only form), its owned hosts and rows, and the calendar runs the first kernel read.
+ * SGN_ESTATE before the first sgn_backlog of the simulation. */
+typedef struct sgn_backlog_timing { double total_ms, kernel_ms[4], copy_ms; uint64_t hosts, rows, calendar_runs; } sgn_backlog_timing;
+int sgn_backlog_timing_get(sgn_ctx* ctx, sgn_backlog_timing* out);
+
 /* ------------------------------------------------------------------------------------ */
 /* CPU-resident applications (SGN_TRAFFIC_EXTERNAL)                                      */
 /* ------------------------------------------------------------------------------------ */

@@ -813,6 +813,14 @@ struct sgn_ctx {
   std::vector<sgn_sample_info> smp_infos;
   hipEvent_t smp_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   sgn_sample_timing smp_timing{};         // of the last sgn_sample (copy_ms: of the last sgn_sample_take)
+  // the backlog report (backlog.hip): its device scratch (header, per-slot calendar lines, per-wave
+  // words, rows), the pinned staging buffer of its copies, and the HIP events of the timing.
+  // Allocated by the first sgn_backlog of a simulation, dropped by sgn_sim_init (backlog_release).
+  void* bk_scratch = nullptr;
+  void* bk_stage = nullptr;
+  hipEvent_t bk_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool bk_timed = false;                  // bk_timing is of a sgn_backlog of this simulation
+  sgn_backlog_timing bk_timing{};
   uint64_t drain_cap = 0;                 // sgn_drain_enable (EXTERNAL traffic)
   std::vector<uint64_t> handles;          // sgn_submit handles by slot (tag & ~SGN_TAG_EXT)
   std::vector<uint32_t> submit_seq;       // per owned host: submissions so far
@@ -1012,6 +1020,8 @@ int inject_runs(sgn_ctx* ctx, const std::vector<EvRec>& runs);  // into the cale
 int trace_view_set(sgn_ctx* ctx, uint64_t base);
 // ---- sample.hip: the interval sampler's buffers and events (free_sim: a new simulation has none) ----
 void sample_release(sgn_ctx* ctx);
+// ---- backlog.hip: the backlog report's scratch, staging buffer and events (free_sim) ----
+void backlog_release(sgn_ctx* ctx);
 // records of the context's trace buffer that a reader may copy now: [trace_base, min(n, trace_base
 // + trace_cap)) for a control block that counts n (n below the cursor: none)
 inline uint64_t trace_held(const sgn_ctx* ctx, uint64_t n) {
@@ -1041,6 +1051,7 @@ uint64_t layout_sig_interop();
 uint64_t layout_sig_snapshot_file();
 uint64_t layout_sig_trace_take();
 uint64_t layout_sig_sample();
+uint64_t layout_sig_backlog();
 }  // namespace sgn
 
 #define SGN_HIP(ctx, call)                                   \

@@ -161,6 +161,38 @@ assert SAMPLE_ROW_DTYPE.itemsize == C.sizeof(SampleRow) == 64
 assert SAMPLE_INFO_DTYPE.itemsize == C.sizeof(SampleInfo) == 104
 
 
+BACKLOG_ROUTER_HELD, BACKLOG_OUT_HELD = 1, 2
+# sgn_backlog_info::total, in order
+BACKLOG_TOTALS = ("router_packets", "router_bytes", "router_held", "send_packets", "send_bytes", "out_held",
+                  "inflight_packets", "submit_pending")
+_BACKLOG_ROW = [("host", "u4"), ("flags", "u4"), ("router_packets", "u4"), ("send_packets", "u4"), ("router_bytes", "u8"),
+                ("send_bytes", "u8"), ("router_oldest", "u8"), ("inflight_packets", "u4"), ("submit_pending", "u4"),
+                ("inflight_earliest", "u8"), ("inflight_latest", "u8")]
+_BACKLOG_INFO = [("rounds", "u8"), ("window_start", "u8"), ("window_end", "u8"), ("hosts", "u8"), ("rows", "u8"),
+                 ("total", "u8", 8), ("max_router_packets", "u8"), ("max_router_host", "u4"), ("pad0", "u4"),
+                 ("max_sojourn_ns", "u8"), ("max_sojourn_host", "u4"), ("pad1", "u4"), ("inflight_earliest", "u8")]
+_CT = {"u4": C.c_uint32, "u8": C.c_uint64}
+
+
+class BacklogRow(C.Structure):
+    _fields_ = [(n, _CT[t]) for n, t in _BACKLOG_ROW]
+
+
+class BacklogInfo(C.Structure):
+    _fields_ = [(f[0], _CT[f[1]] * f[2] if len(f) > 2 else _CT[f[1]]) for f in _BACKLOG_INFO]
+
+
+class BacklogTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_double), ("kernel_ms", C.c_double * 4), ("copy_ms", C.c_double),
+                ("hosts", C.c_uint64), ("rows", C.c_uint64), ("calendar_runs", C.c_uint64)]
+
+
+BACKLOG_ROW_DTYPE = np.dtype([(n, "<" + t) for n, t in _BACKLOG_ROW])
+BACKLOG_INFO_DTYPE = np.dtype([(f[0], "<" + f[1], (f[2],)) if len(f) > 2 else (f[0], "<" + f[1]) for f in _BACKLOG_INFO])
+assert BACKLOG_ROW_DTYPE.itemsize == C.sizeof(BacklogRow) == 64
+assert BACKLOG_INFO_DTYPE.itemsize == C.sizeof(BacklogInfo) == 144
+
+
 DIGEST_DTYPE = np.dtype([("tx", "<u8"), ("rx", "<u8"), ("app", "<u8"), ("rng", "<u8", (4,)),
                          ("next_event_id", "<u8"), ("n_sent", "<u8"), ("n_popped", "<u8"),
                          ("n_delivered", "<u8"), ("n_codel_dropped", "<u8")])
@@ -373,6 +405,8 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         "sgn_sample_pending": (C.c_int, [vp, u64p, u64p]),
         "sgn_sample_take": (C.c_int, [vp, C.POINTER(SampleRow), C.c_uint64, u64p, C.POINTER(SampleInfo), C.c_uint64, u64p]),
         "sgn_sample_timing_get": (C.c_int, [vp, C.POINTER(SampleTiming)]),
+        "sgn_backlog": (C.c_int, [vp, C.POINTER(BacklogRow), C.c_uint64, u64p, C.POINTER(BacklogInfo)]),
+        "sgn_backlog_timing_get": (C.c_int, [vp, C.POINTER(BacklogTiming)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -732,6 +766,38 @@ class Context:
         self.check(self.L.sgn_sample_timing_get(self.h, C.byref(t)))
         return {"total_ms": t.total_ms, "kernel_ms": list(t.kernel_ms), "copy_ms": t.copy_ms,
                 "hosts": t.hosts, "rows": t.rows}
+
+    # ---- the backlog report: standing queues and in-flight packets per owned host (sgn_backlog) ----
+    def backlog(self, rows=True, cap=None):
+        """What stands in the network at the round edge the context is at, as a Backlog: .info (the
+        totals and maxima, folded on the device) and .rows (BACKLOG_ROW_DTYPE, one per owned host
+        with anything standing, ascending by host). rows=False asks for the totals only (no row is
+        copied; info["rows"] still counts them). cap: the row array's size (default: the row
+        count, asked for first); too small raises SgnError with rc ERANGE, .needed = the row
+        count and .info = the info, which is filled all the same."""
+        info = BacklogInfo()
+        n = C.c_uint64()
+        if cap is None:
+            self.check(self.L.sgn_backlog(self.h, None, 0, C.byref(n), C.byref(info)))
+            if not rows or n.value == 0:
+                return Backlog(info, None)
+            cap = n.value
+        out = np.zeros(cap, dtype=BACKLOG_ROW_DTYPE)
+        rc = self.L.sgn_backlog(self.h, out.ctypes.data_as(C.POINTER(BacklogRow)) if cap else None, cap, C.byref(n),
+                                C.byref(info))
+        if rc != 0:
+            e = SgnError(rc, self.L.sgn_last_error(self.h).decode())
+            e.needed = n.value
+            e.info = Backlog(info, None).info
+            e.out = out
+            raise e
+        return Backlog(info, out[: n.value] if rows else None)
+
+    def backlog_timing(self):
+        t = BacklogTiming()
+        self.check(self.L.sgn_backlog_timing_get(self.h, C.byref(t)))
+        return {"total_ms": t.total_ms, "kernel_ms": list(t.kernel_ms), "copy_ms": t.copy_ms,
+                "hosts": t.hosts, "rows": t.rows, "calendar_runs": t.calendar_runs}
 
     # ---- CPU-resident applications (TRAFFIC_EXTERNAL) and the host RNG ----
     def drain_enable(self, cap):
@@ -1106,16 +1172,48 @@ class Samples:
         return np.cumsum(self.dense(field, n_hosts), axis=0, dtype=np.uint64)
 
 
-def run_sampled(ctx_or_shards, interval_ns, until=None):
+class Backlog:
+    """One backlog report (Context.backlog): .info, a dict of sgn_backlog_info (total: the eight sums
+    in BACKLOG_TOTALS order; .totals: the same by name), and .rows (BACKLOG_ROW_DTYPE, ascending by
+    host; empty for the totals-only form)."""
+
+    def __init__(self, info, rows=None):
+        self.info = {f[0]: ([int(v) for v in getattr(info, f[0])] if len(f) > 2 else int(getattr(info, f[0])))
+                     for f in _BACKLOG_INFO if not f[0].startswith("pad")}
+        self.rows = np.zeros(0, BACKLOG_ROW_DTYPE) if rows is None else np.ascontiguousarray(rows, dtype=BACKLOG_ROW_DTYPE)
+
+    @property
+    def totals(self):
+        return dict(zip(BACKLOG_TOTALS, self.info["total"]))
+
+    def dense(self, field, n_hosts=None):
+        """The field of every host, indexed by HostId, zeros where no row exists (also for the two
+        times that are SGN_EMUTIME_INVALID in a row without them). n_hosts: the array's length —
+        default the owned hosts, which covers an unsharded context; a shard's rows need the
+        simulation's host count."""
+        n = int(self.info["hosts"]) if n_hosts is None else int(n_hosts)
+        out = np.zeros(n, dtype=BACKLOG_ROW_DTYPE.fields[field][0])
+        v = self.rows[field].copy()
+        if field in ("router_oldest", "inflight_earliest"):
+            v[v == EMUTIME_INVALID] = 0
+        out[self.rows["host"]] = v
+        return out
+
+
+def run_sampled(ctx_or_shards, interval_ns, until=None, backlog=False):
     """Runs a Context — or this process's shards, as shards_run_until takes them — to the end, or
     until the next window would start at or after `until`, sampling at every multiple of
     interval_ns of simulated time at which anything was left to run: run_until the next multiple
     above the window start, then sample() on every context (sample_enable first; its row capacity
     need only hold a few samples: the rows are taken when they pass half of it, and at the end).
-    Returns the Samples of the context, or a list of them, one per shard."""
+    Returns the Samples of the context, or a list of them, one per shard.
+    backlog=True: after each sample the backlog totals are taken too (Context.backlog(rows=False))
+    and every returned Samples carries backlog_total[samples, 8] (BACKLOG_TOTALS order; summed over
+    the shards) and backlog_max_router[samples] (the largest CoDel queue; the shards' maximum)."""
     many = isinstance(ctx_or_shards, (list, tuple))
     ctxs = list(ctx_or_shards) if many else [ctx_or_shards]
     takes = [[] for _ in ctxs]
+    bl_total, bl_max = [], []
     while True:
         ws, _, active = ctxs[0].window()
         if not active or (until is not None and ws >= until):
@@ -1136,9 +1234,17 @@ def run_sampled(ctx_or_shards, interval_ns, until=None):
                 c.sample()
             if 2 * c.sample_pending()[0] > c.sample_capacity:
                 tk.append(c.sample_take())
+        if backlog:  # the totals-only form on every context, after the sample
+            infos = [c.backlog(rows=False).info for c in ctxs]
+            bl_total.append(np.sum([i["total"] for i in infos], axis=0, dtype=np.uint64))
+            bl_max.append(max(i["max_router_packets"] for i in infos))
     for c, tk in zip(ctxs, takes):
         tk.append(c.sample_take())
     out = [Samples.from_takes(tk) for tk in takes]
+    if backlog:
+        for s in out:
+            s.backlog_total = np.array(bl_total, dtype=np.uint64).reshape(len(bl_total), 8)
+            s.backlog_max_router = np.array(bl_max, dtype=np.uint64)
     return out if many else out[0]
 
 
