@@ -982,6 +982,11 @@ int64_t sgn_pcap_write_trace(sgn_pcap* p, const sgn_trace_rec* recs, uint64_t n,
  * (router/codel_queue.rs:285-298), for checking device f64 rounding against the host. */
 int sgn_selftest_codel_law(sgn_ctx* ctx, uint64_t n, uint64_t* out);
 
+/* The reports' exclusive scan (sgn_sample's scan kernel itself, one workgroup walking the counts in
+ * tiles of 1024) on the caller's n counts: off_out[j] = counts[0] + ... + counts[j - 1], *total_out
+ * their sum. Needs no simulation; for checking the carry from tile to tile. */
+int sgn_selftest_report_scan(sgn_ctx* ctx, const uint32_t* counts, uint32_t n, uint32_t* off_out, uint64_t* total_out);
+
 /* The section digest of snapshot files, for len % 4 == 0: with w_j the little-endian u64 at byte
  * 8j (a 4-byte tail zero-extended), D = mix64(len ^ SGN_DIGEST_SEED) + sum_j mix64(w_j ^
  * (0x9e3779b97f4a7c15 * (j + 1))) mod 2^64 (sgn_mix64, sgn_workload.h): position-keyed terms under

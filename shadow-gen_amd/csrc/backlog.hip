@@ -31,20 +31,19 @@
 #include <cstring>
 #include <string>
 
-#include "sgn_internal.h"
+#include "report_common.h"
 #include "sgn_workload.h"
 
 using namespace sgn;
+using namespace sgn::report;  // the scan (kScanTile = 1024 waves a tile), the wave reductions, the host scaffolding
 
 // ---- device side ----------------------------------------------------------------------------
 namespace {
 
-constexpr uint32_t kCalThreads = 256;                 // k_backlog_calendar: four waves, a bucket each
-constexpr uint32_t kBkThreads = 256;                  // k_backlog_count, _scatter: one lane per host
-constexpr uint32_t kScanThreads = 256, kScanPer = 4;  // k_backlog_scan: one workgroup, tiles of 1024 waves
-constexpr uint32_t kScanTile = kScanThreads * kScanPer;
+constexpr uint32_t kCalThreads = 256;      // k_backlog_calendar: four waves, a bucket each
+constexpr uint32_t kBkThreads = 256;       // k_backlog_count, _scatter: one lane per host
 constexpr uint32_t kTotals = 8;
-constexpr uint64_t kStageRows = 1u << 16;             // rows per piece of the device-to-host copy (4 MB)
+constexpr uint64_t kStageRows = 1u << 16;  // rows per piece of the device-to-host copy (4 MB)
 
 static_assert(sizeof(sgn_backlog_row) == 64 && offsetof(sgn_backlog_row, router_bytes) == 16 &&
                   offsetof(sgn_backlog_row, router_oldest) == 32 && offsetof(sgn_backlog_row, inflight_earliest) == 48,
@@ -98,12 +97,6 @@ struct BkArgs {
   uint32_t lo, nH, n_all, NB, G, CAP, gsh, fifo_cap, cq_pages, tkind;
 };
 
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void bk_fail(BkHdr* hdr, uint32_t bit, uint64_t what) {
-  if ((atomicOr(&hdr->err, bit) & bit) == 0) hdr->err_info = what;
-}
-
 // 1. the calendar pass. A group's pending runs are in its slab of each of the NB buckets (between
 // rounds the spare slab set is empty): the workgroup's waves take the buckets in turn, a wave's
 // lanes the slab's runs. A run addresses a slot of this group (the calendar is laid out by the
@@ -128,7 +121,7 @@ __global__ __launch_bounds__(kCalThreads) void k_backlog_calendar(BkArgs a, BkCa
   for (uint32_t b = wv; b < a.NB; b += kCalThreads / 64) {
     const uint32_t sl = a.bucket_slab[b];
     if (sl > a.NB) {  // (NB + 1 slab sets)
-      if (lane == 0) bk_fail(hdr, BK_ESLAB, (uint64_t)b);
+      if (lane == 0) report_fail(&hdr->err, &hdr->err_info, BK_ESLAB, (uint64_t)b);
       continue;
     }
     const uint64_t idx = (uint64_t)sl * a.G + g;  // (< (NB + 1) * G: sl <= NB, g < G)
@@ -141,7 +134,7 @@ __global__ __launch_bounds__(kCalThreads) void k_backlog_calendar(BkArgs a, BkCa
     // a fill above the slab's room (runs in the spill area: the host resolves them before the call)
     // or an extension outside its pool: reported; what lies inside the buffers is still read
     if (fill - np != ne || (ne && (eo > a.ext_total || ne > a.ext_total - eo))) {
-      if (lane == 0) bk_fail(hdr, BK_ESLAB, idx);
+      if (lane == 0) report_fail(&hdr->err, &hdr->err_info, BK_ESLAB, idx);
       if (ne && (eo > a.ext_total || ne > a.ext_total - eo)) ne = 0;
     }
     for (uint32_t j = lane; j < np + ne; j += 64) {
@@ -151,7 +144,7 @@ __global__ __launch_bounds__(kCalThreads) void k_backlog_calendar(BkArgs a, BkCa
       const uint32_t src = (uint32_t)hi2.x, dst = (uint32_t)(hi2.x >> 32), pc = (uint32_t)hi2.y;
       const uint32_t k = dst - a.lo - slot0;  // the slot within the group
       if (k >= gsz || slot0 + k >= a.nH) {
-        bk_fail(hdr, BK_EDST, idx);
+        report_fail(&hdr->err, &hdr->err_info, BK_EDST, idx);
         continue;
       }
       const uint32_t n = pc >> 16;
@@ -229,7 +222,7 @@ __device__ __forceinline__ BkCal bk_cal(const BkCal* cal, uint32_t slot) {
 __device__ __forceinline__ uint64_t bk_oldest(const BkArgs& a, const BkHost& h, uint32_t host, BkHdr* hdr) {
   if (h.cq_len == 0) return INVALID;
   if (h.cq_head >= (uint64_t)a.cq_pages * CQ_PAGE) {
-    bk_fail(hdr, BK_EQUEUE, host);
+    report_fail(&hdr->err, &hdr->err_info, BK_EQUEUE, host);
     return INVALID;
   }
   return a.codel[h.cq_head].enqueue_ts;
@@ -251,21 +244,13 @@ __global__ __launch_bounds__(kBkThreads) void k_backlog_count(BkArgs a, const Bk
       if (h.cq_len) maxq = (uint64_t)h.cq_len << 32 | (uint32_t)~(a.lo + i);
       old = bk_oldest(a, h, a.lo + i, hdr);
     } else {
-      bk_fail(hdr, BK_ESLOT, a.lo + i);
+      report_fail(&hdr->err, &hdr->err_info, BK_ESLOT, a.lo + i);
     }
   }
   const uint64_t m = __ballot(row);
   uint32_t oh = a.lo + i;  // (lanes ascend by HostId: on equal times the lower lane's host stays)
-#pragma unroll
-  for (uint32_t x = 1; x < 64; x <<= 1) {
-    const uint64_t mq = __shfl_xor(maxq, x), mo = __shfl_xor(old, x);
-    const uint32_t mh = __shfl_xor(oh, x);
-    maxq = mq > maxq ? mq : maxq;
-    if (mo < old || (mo == old && mh < oh)) {
-      old = mo;
-      oh = mh;
-    }
-  }
+  maxq = wave_max(maxq);
+  wave_argmin(old, oh);
   if (lane == 0 && i < a.nH) {
     wave_cnt[i >> 6] = (uint32_t)__popcll(m);
     wave_maxq[i >> 6] = maxq;
@@ -274,62 +259,25 @@ __global__ __launch_bounds__(kBkThreads) void k_backlog_count(BkArgs a, const Bk
   }
 }
 
-// 3. one workgroup walks the nW wave words in tiles of kScanTile, carrying the running total:
-// wave_off[w] = hosts with a row in the waves before w; and folds the waves' maxima
+// 3. one workgroup scans the nW wave counts (tiled_scan): wave_off[w] = hosts with a row in the waves
+// before w; and folds the waves' maxima
 __global__ __launch_bounds__(kScanThreads) void k_backlog_scan(const uint32_t* __restrict__ wave_cnt, const uint64_t* __restrict__ wave_maxq,
                                                                const uint64_t* __restrict__ wave_old,
                                                                const uint32_t* __restrict__ wave_old_host, uint32_t nW,
                                                                uint32_t* __restrict__ wave_off, BkHdr* __restrict__ hdr) {
-  __shared__ uint32_t ws[kScanThreads / 64];
   __shared__ uint64_t s_maxq[kScanThreads], s_old[kScanThreads];
   __shared__ uint32_t s_oh[kScanThreads];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint32_t carry = 0;  // (the same in every thread; at most nH < 2^32)
   uint64_t maxq = 0, old = INVALID;
   uint32_t oh = 0xFFFFFFFFu;
-  for (uint32_t t0 = 0; t0 < nW; t0 += kScanTile) {
-    const uint32_t j0 = t0 + threadIdx.x * kScanPer;
-    uint32_t c[kScanPer];
-    uint32_t tc = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kScanPer; j++) {
-      c[j] = 0;
-      if (j0 + j < nW) {
-        c[j] = wave_cnt[j0 + j];
-        const uint64_t mq = wave_maxq[j0 + j], mo = wave_old[j0 + j];
-        const uint32_t mh = wave_old_host[j0 + j];
+  const uint32_t rows = tiled_scan<uint32_t>(
+      nW,
+      [&](uint32_t j) {
+        const uint64_t mq = wave_maxq[j];
         maxq = mq > maxq ? mq : maxq;
-        if (mo < old || (mo == old && mh < oh)) {
-          old = mo;
-          oh = mh;
-        }
-      }
-      tc += c[j];
-    }
-    uint32_t ic = tc;  // inclusive scan over the wave, then over the workgroup's waves
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t v = __shfl_up(ic, d);
-      if (lane >= d) ic += v;
-    }
-    if (lane == 63) ws[w] = ic;
-    __syncthreads();
-    uint32_t e = carry, tot = 0;
-#pragma unroll
-    for (uint32_t v = 0; v < kScanThreads / 64; v++) {
-      if (v < w) e += ws[v];
-      tot += ws[v];
-    }
-    e += ic - tc;
-#pragma unroll
-    for (uint32_t j = 0; j < kScanPer; j++) {
-      if (j0 + j >= nW) break;
-      wave_off[j0 + j] = e;
-      e += c[j];
-    }
-    carry += tot;
-    __syncthreads();  // (the next tile writes ws)
-  }
+        argmin_fold(old, oh, wave_old[j], wave_old_host[j]);
+        return wave_cnt[j];
+      },
+      [&](uint32_t j, uint32_t before, uint32_t) { wave_off[j] = before; });
   s_maxq[threadIdx.x] = maxq;
   s_old[threadIdx.x] = old;
   s_oh[threadIdx.x] = oh;
@@ -337,12 +285,9 @@ __global__ __launch_bounds__(kScanThreads) void k_backlog_scan(const uint32_t* _
   if (threadIdx.x == 0) {
     for (uint32_t t = 1; t < kScanThreads; t++) {
       maxq = s_maxq[t] > maxq ? s_maxq[t] : maxq;
-      if (s_old[t] < old || (s_old[t] == old && s_oh[t] < oh)) {
-        old = s_old[t];
-        oh = s_oh[t];
-      }
+      argmin_fold(old, oh, s_old[t], s_oh[t]);
     }
-    hdr->rows = carry;
+    hdr->rows = rows;
     hdr->max_router = maxq >> 32;
     hdr->max_router_host = maxq ? ~(uint32_t)maxq : 0u;
     hdr->min_oldest = old;
@@ -378,7 +323,7 @@ __global__ __launch_bounds__(kBkThreads) void k_backlog_scatter(BkArgs a, const 
     uint32_t sp = 0;
     uint64_t sb = 0;
     if (h.fq_len > a.fifo_cap || h.fq_head >= a.fifo_cap) {
-      bk_fail(hdr, BK_EQUEUE, host);
+      report_fail(&hdr->err, &hdr->err_info, BK_EQUEUE, host);
     } else {
       const FifoEnt* ring = a.fifo + (size_t)h.slot * a.fifo_cap;
       uint32_t idx = h.fq_head;
@@ -402,7 +347,7 @@ __global__ __launch_bounds__(kBkThreads) void k_backlog_scatter(BkArgs a, const 
     t[7] = c.submit;
     earliest = c.packets ? c.earliest : INVALID;
     if (rows) {
-      const uint64_t j = (uint64_t)wave_off[i >> 6] + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+      const uint64_t j = (uint64_t)wave_off[i >> 6] + rank_below(m, lane);
       if (j < cap) {
         u64x2* p = (u64x2*)(rows + j);
         p[0] = u64x2{(uint64_t)host | (uint64_t)h.flags << 32, (uint64_t)h.cq_len | (uint64_t)sp << 32};
@@ -410,22 +355,16 @@ __global__ __launch_bounds__(kBkThreads) void k_backlog_scatter(BkArgs a, const 
         p[2] = u64x2{oldest, (uint64_t)c.packets | (uint64_t)c.submit << 32};
         p[3] = u64x2{earliest, c.packets ? c.latest : 0ull};
       } else {
-        bk_fail(hdr, BK_EROW, host);
+        report_fail(&hdr->err, &hdr->err_info, BK_EROW, host);
       }
     }
   }
 #pragma unroll
   for (uint32_t k = 0; k < kTotals; k++) {
-    uint64_t s = t[k];
-#pragma unroll
-    for (uint32_t x = 32; x > 0; x >>= 1) s += __shfl_xor(s, x);
+    const uint64_t s = wave_sum(t[k]);
     if (lane == 0 && s) atomicAdd((unsigned long long*)&hdr->total[k], (unsigned long long)s);
   }
-#pragma unroll
-  for (uint32_t x = 32; x > 0; x >>= 1) {
-    const uint64_t v = __shfl_xor(earliest, x);
-    earliest = v < earliest ? v : earliest;
-  }
+  earliest = wave_min(earliest);
   if (lane == 0 && earliest != INVALID) atomicMin((unsigned long long*)&hdr->inflight_earliest, (unsigned long long)earliest);
 }
 
@@ -440,24 +379,20 @@ struct BkLay {
 };
 BkLay bk_lay(uint32_t nH) {
   const size_t nW = ((size_t)nH + 63) / 64;
-  auto up = [](size_t v) { return (v + 127) & ~(size_t)127; };
+  ScratchLay s;  // (every piece on a 128-byte line of its own)
   BkLay l;
-  l.hdr = 0;
-  l.cal = sizeof(BkHdr);
-  l.cnt = l.cal + up((size_t)nH * sizeof(BkCal));
-  l.off = l.cnt + up(nW * 4);
-  l.maxq = l.off + up(nW * 4);
-  l.old = l.maxq + up(nW * 8);
-  l.oldh = l.old + up(nW * 8);
-  l.rows = l.oldh + up(nW * 4);
-  l.bytes = l.rows + up((size_t)nH * sizeof(sgn_backlog_row));
+  l.hdr = s.take(sizeof(BkHdr), 128);
+  l.cal = s.take((size_t)nH * sizeof(BkCal), 128);
+  l.cnt = s.take(nW * 4, 128);
+  l.off = s.take(nW * 4, 128);
+  l.maxq = s.take(nW * 8, 128);
+  l.old = s.take(nW * 8, 128);
+  l.oldh = s.take(nW * 4, 128);
+  l.rows = s.take((size_t)nH * sizeof(sgn_backlog_row), 128);
+  l.bytes = s.take(0, 128);
   return l;
 }
 size_t bk_stage_bytes(uint32_t nH) { return sizeof(BkHdr) + std::min<uint64_t>(std::max<uint32_t>(nH, 1u), kStageRows) * sizeof(sgn_backlog_row); }
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 BkArgs bk_args(const sgn_ctx* ctx) {
   const DevSim& S = ctx->S;
@@ -506,12 +441,10 @@ int bk_ensure(sgn_ctx* ctx) {
     backlog_release(ctx);
     return set_error(ctx, SGN_ENOMEM, "allocation failed (sgn_backlog)");
   }
-  for (hipEvent_t& e : ctx->bk_ev)
-    if (hipEventCreate(&e) != hipSuccess) {
-      e = nullptr;
-      backlog_release(ctx);
-      return set_error(ctx, SGN_EDEVICE, "hipEventCreate failed (sgn_backlog)");
-    }
+  if (!ctx->bk_ev.make()) {
+    backlog_release(ctx);
+    return set_error(ctx, SGN_EDEVICE, "hipEventCreate failed (sgn_backlog)");
+  }
   return 0;
 }
 
@@ -523,10 +456,7 @@ void backlog_release(sgn_ctx* ctx) {
   if (ctx->bk_scratch) (void)hipFree(ctx->bk_scratch);
   if (ctx->bk_stage) (void)hipHostFree(ctx->bk_stage);
   ctx->bk_scratch = ctx->bk_stage = nullptr;
-  for (hipEvent_t& e : ctx->bk_ev) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
-  }
+  ctx->bk_ev.release();
   ctx->bk_timed = false;
   ctx->bk_timing = sgn_backlog_timing{};
 }
@@ -572,7 +502,7 @@ int sgn_backlog(sgn_ctx* ctx, sgn_backlog_row* out, uint64_t cap, uint64_t* n_ou
   sgn_backlog_row* h_rows = (sgn_backlog_row*)((char*)ctx->bk_stage + sizeof(BkHdr));
   const BkArgs a = bk_args(ctx);
   hipStream_t st = ctx->stream;
-  hipEvent_t* ev = ctx->bk_ev;
+  const ReportEvents<8>& ev = ctx->bk_ev;
   const uint32_t blocks = (nH + kBkThreads - 1) / kBkThreads;
   std::memset(h, 0, sizeof(BkHdr));
   h->inflight_earliest = INVALID;
@@ -586,9 +516,7 @@ int sgn_backlog(sgn_ctx* ctx, sgn_backlog_row* out, uint64_t cap, uint64_t* n_ou
     hipLaunchKernelGGL(k_backlog_scan, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t*)d_cnt, (const uint64_t*)d_maxq,
                        (const uint64_t*)d_old, (const uint32_t*)d_oldh, nW, d_off, d_hdr);
     (void)hipEventRecord(ev[3], st);
-    SGN_HIP(ctx, hipGetLastError());
-    SGN_HIP(ctx, hipMemcpyAsync(h, d_hdr, sizeof(BkHdr), hipMemcpyDeviceToHost, st));
-    SGN_HIP(ctx, hipStreamSynchronize(st));
+    if ((rc = read_header(ctx, d_hdr, h))) return rc;
     if (h->err) return bk_bad(ctx, *h);
     if (h->rows > nH) return set_error(ctx, SGN_EDEVICE, "sgn_backlog: the wave counts add up to more rows than hosts");
   }
@@ -599,9 +527,7 @@ int sgn_backlog(sgn_ctx* ctx, sgn_backlog_row* out, uint64_t cap, uint64_t* n_ou
     hipLaunchKernelGGL(k_backlog_scatter, dim3(blocks), dim3(kBkThreads), 0, st, a, (const BkCal*)d_cal, (const uint32_t*)d_off,
                        want_rows ? d_rows : (sgn_backlog_row*)nullptr, (uint64_t)nH, d_hdr);
     (void)hipEventRecord(ev[5], st);
-    SGN_HIP(ctx, hipGetLastError());
-    SGN_HIP(ctx, hipMemcpyAsync(h, d_hdr, sizeof(BkHdr), hipMemcpyDeviceToHost, st));
-    SGN_HIP(ctx, hipStreamSynchronize(st));
+    if ((rc = read_header(ctx, d_hdr, h))) return rc;
     if (h->err) return bk_bad(ctx, *h);
   }
   sgn_backlog_info in{};
@@ -622,11 +548,10 @@ int sgn_backlog(sgn_ctx* ctx, sgn_backlog_row* out, uint64_t cap, uint64_t* n_ou
   *info = in;
   *n_out = rows;
   sgn_backlog_timing T{};
-  float ms = 0;
-  if (nH && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) T.kernel_ms[0] = ms;
-  if (nH && hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) T.kernel_ms[1] = ms;
-  if (nH && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) T.kernel_ms[2] = ms;
-  if (rows && hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess) T.kernel_ms[3] = ms;
+  if (nH) T.kernel_ms[0] = elapsed_ms(ev[0], ev[1]);
+  if (nH) T.kernel_ms[1] = elapsed_ms(ev[1], ev[2]);
+  if (nH) T.kernel_ms[2] = elapsed_ms(ev[2], ev[3]);
+  if (rows) T.kernel_ms[3] = elapsed_ms(ev[4], ev[5]);
   T.hosts = nH;
   T.rows = rows;
   T.calendar_runs = calendar_runs;
@@ -647,7 +572,7 @@ int sgn_backlog(sgn_ctx* ctx, sgn_backlog_row* out, uint64_t cap, uint64_t* n_ou
     }
     (void)hipEventRecord(ev[7], st);
     SGN_HIP(ctx, hipStreamSynchronize(st));
-    if (hipEventElapsedTime(&ms, ev[6], ev[7]) == hipSuccess) T.copy_ms = ms;
+    T.copy_ms = elapsed_ms(ev[6], ev[7]);
   }
   T.total_ms = ms_since(t_begin);
   ctx->bk_timing = T;

@@ -27,16 +27,15 @@
 #include <cstring>
 #include <string>
 
-#include "sgn_internal.h"
+#include "report_common.h"
 
 using namespace sgn;
+using namespace sgn::report;  // the scan (kScanTile = 1024 waves a tile), the wave reductions, the host scaffolding
 
 // ---- device side ----------------------------------------------------------------------------
 namespace {
 
-constexpr uint32_t kSmpThreads = 256;                  // k_sample_count, _scatter, _rebase: one lane per host
-constexpr uint32_t kScanThreads = 256, kScanPer = 4;   // k_sample_scan: one workgroup, tiles of 1024 waves
-constexpr uint32_t kScanTile = kScanThreads * kScanPer;
+constexpr uint32_t kSmpThreads = 256;  // k_sample_count, _scatter, _rebase: one lane per host
 constexpr uint32_t kCounters = 7;
 
 static_assert(sizeof(sgn_sample_row) == 64 && offsetof(sgn_sample_row, sent) == 8 && offsetof(sgn_sample_row, blocked) == 56,
@@ -72,12 +71,6 @@ struct SmpArgs {
   uint32_t lo, nH;
 };
 
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void smp_fail(SmpHdr* hdr, uint32_t bit, uint32_t host) {
-  if ((atomicOr(&hdr->err, bit) & bit) == 0) hdr->err_host = host;
-}
-
 // the seven counters of owned host i (HostId lo + i); false: its slot is not this shard's
 __device__ __forceinline__ bool load_counters(const SmpArgs& a, uint32_t i, uint64_t c[kCounters]) {
   const uint32_t slot = a.sid_of[a.lo + i] - a.lo;
@@ -110,54 +103,20 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_count(SmpArgs a, uint32_
 #pragma unroll
       for (uint32_t k = 0; k < kCounters; k++) changed |= c[k] != a.base[(size_t)k * a.nH + i];
     } else {
-      smp_fail(hdr, SMP_ESLOT, a.lo + i);
+      report_fail(&hdr->err, &hdr->err_host, SMP_ESLOT, a.lo + i);
     }
   }
   const uint64_t m = __ballot(changed);
   if ((threadIdx.x & 63u) == 0 && i < a.nH) wave_cnt[i >> 6] = (uint32_t)__popcll(m);
 }
 
-// 2. one workgroup walks the nW wave counts in tiles of kScanTile, carrying the running total:
+// 2. one workgroup scans the nW wave counts (tiled_scan; the total is at most nH < 2^32):
 // wave_off[w] = changed hosts of the waves before w
 __global__ __launch_bounds__(kScanThreads) void k_sample_scan(const uint32_t* __restrict__ wave_cnt, uint32_t nW,
                                                               uint32_t* __restrict__ wave_off, SmpHdr* __restrict__ hdr) {
-  __shared__ uint32_t ws[kScanThreads / 64];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint32_t carry = 0;  // (the same in every thread; at most nH < 2^32)
-  for (uint32_t t0 = 0; t0 < nW; t0 += kScanTile) {
-    const uint32_t j0 = t0 + threadIdx.x * kScanPer;
-    uint32_t c[kScanPer];
-    uint32_t tc = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kScanPer; j++) {
-      c[j] = j0 + j < nW ? wave_cnt[j0 + j] : 0;
-      tc += c[j];
-    }
-    uint32_t ic = tc;  // inclusive scan over the wave, then over the workgroup's waves
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t v = __shfl_up(ic, d);
-      if (lane >= d) ic += v;
-    }
-    if (lane == 63) ws[w] = ic;
-    __syncthreads();
-    uint32_t e = carry, tot = 0;
-#pragma unroll
-    for (uint32_t v = 0; v < kScanThreads / 64; v++) {
-      if (v < w) e += ws[v];
-      tot += ws[v];
-    }
-    e += ic - tc;
-#pragma unroll
-    for (uint32_t j = 0; j < kScanPer; j++) {
-      if (j0 + j >= nW) break;
-      wave_off[j0 + j] = e;
-      e += c[j];
-    }
-    carry += tot;
-    __syncthreads();  // (the next tile writes ws)
-  }
-  if (threadIdx.x == 0) hdr->rows = carry;
+  const uint32_t rows = tiled_scan<uint32_t>(
+      nW, [&](uint32_t j) { return wave_cnt[j]; }, [&](uint32_t j, uint32_t before, uint32_t) { wave_off[j] = before; });
+  if (threadIdx.x == 0) hdr->rows = rows;
 }
 
 // 3. rows, baseline, totals. The flags are those of k_sample_count (nothing ran in between), so
@@ -181,7 +140,7 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_scatter(SmpArgs a, const
   const uint64_t m = __ballot(changed);
   if (m == 0) return;  // (the whole wave: nothing to write, nothing to add)
   if (changed) {
-    const uint64_t j = first + wave_off[i >> 6] + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+    const uint64_t j = first + wave_off[i >> 6] + rank_below(m, lane);
     if (j < cap) {
       u64x2* p = (u64x2*)(rows + j);
       p[0] = u64x2{(uint64_t)(a.lo + i) | (uint64_t)sample << 32, d[0]};
@@ -192,16 +151,14 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_scatter(SmpArgs a, const
       for (uint32_t k = 0; k < kCounters; k++)
         if (d[k]) a.base[(size_t)k * a.nH + i] = c[k];
     } else {
-      smp_fail(hdr, SMP_EROW, a.lo + i);
+      report_fail(&hdr->err, &hdr->err_host, SMP_EROW, a.lo + i);
 #pragma unroll
       for (uint32_t k = 0; k < kCounters; k++) d[k] = 0;
     }
   }
 #pragma unroll
   for (uint32_t k = 0; k < kCounters; k++) {
-    uint64_t s = d[k];
-#pragma unroll
-    for (uint32_t x = 32; x > 0; x >>= 1) s += __shfl_xor(s, x);
+    const uint64_t s = wave_sum(d[k]);
     if (lane == 0 && s) atomicAdd((unsigned long long*)&hdr->total[k], (unsigned long long)s);
   }
 }
@@ -212,7 +169,7 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_rebase(SmpArgs a, SmpHdr
   if (i >= a.nH) return;
   uint64_t c[kCounters];
   if (!load_counters(a, i, c)) {
-    smp_fail(hdr, SMP_ESLOT, a.lo + i);
+    report_fail(&hdr->err, &hdr->err_host, SMP_ESLOT, a.lo + i);
     return;
   }
 #pragma unroll
@@ -228,18 +185,14 @@ namespace {
 struct SmpLay {
   size_t hdr, cnt, off, bytes;
 };
-SmpLay smp_lay(uint32_t nH) {
-  const size_t nW = ((size_t)nH + 63) / 64;
+SmpLay smp_lay(size_t nW) {
+  ScratchLay s;
   SmpLay l;
-  l.hdr = 0;
-  l.cnt = sizeof(SmpHdr);
-  l.off = l.cnt + ((nW * 4 + 15) & ~(size_t)15);
-  l.bytes = l.off + ((nW * 4 + 15) & ~(size_t)15);
+  l.hdr = s.take(sizeof(SmpHdr), 16);
+  l.cnt = s.take(nW * 4, 16);
+  l.off = s.take(nW * 4, 16);
+  l.bytes = s.take(0, 16);
   return l;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 SmpArgs smp_args(const sgn_ctx* ctx) {
@@ -274,10 +227,8 @@ int smp_rebase(sgn_ctx* ctx, const char* what) {
   hipStream_t st = ctx->stream;
   SGN_HIP(ctx, hipMemsetAsync(d_hdr, 0, sizeof(SmpHdr), st));
   if (nH) hipLaunchKernelGGL(k_sample_rebase, dim3((nH + kSmpThreads - 1) / kSmpThreads), dim3(kSmpThreads), 0, st, smp_args(ctx), d_hdr);
-  SGN_HIP(ctx, hipGetLastError());
   SmpHdr h{};
-  SGN_HIP(ctx, hipMemcpyAsync(&h, d_hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-  SGN_HIP(ctx, hipStreamSynchronize(st));
+  if (int rc = read_header(ctx, d_hdr, &h)) return rc;
   if (h.err) return smp_bad(ctx, what, h);
   ctx->smp_base_rounds = ctx->h_ctrl->rounds;
   ctx->smp_stale = false;
@@ -293,10 +244,7 @@ void sample_release(sgn_ctx* ctx) {
   if (ctx->smp_base) (void)hipFree(ctx->smp_base);
   if (ctx->smp_scratch) (void)hipFree(ctx->smp_scratch);
   ctx->smp_rows = ctx->smp_base = ctx->smp_scratch = nullptr;
-  for (hipEvent_t& e : ctx->smp_ev) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
-  }
+  ctx->smp_ev.release();
   ctx->smp_cap = ctx->smp_pending = 0;
   ctx->smp_index = ctx->smp_base_rounds = 0;
   ctx->smp_stale = false;
@@ -317,7 +265,7 @@ int sgn_sample_enable(sgn_ctx* ctx, uint64_t row_capacity) {
   SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
   sample_release(ctx);
   const uint32_t nH = ctx->S.nH;
-  const SmpLay L = smp_lay(nH);
+  const SmpLay L = smp_lay(((size_t)nH + 63) / 64);
   bool ok = hipMalloc(&ctx->smp_rows, row_capacity * sizeof(sgn_sample_row)) == hipSuccess;
   ok = ok && hipMalloc(&ctx->smp_base, std::max<size_t>(16, (size_t)kCounters * nH * 8)) == hipSuccess;
   ok = ok && hipMalloc(&ctx->smp_scratch, L.bytes) == hipSuccess;
@@ -326,12 +274,10 @@ int sgn_sample_enable(sgn_ctx* ctx, uint64_t row_capacity) {
     sample_release(ctx);
     return set_error(ctx, SGN_ENOMEM, "device allocation failed (sgn_sample_enable)");
   }
-  for (hipEvent_t& e : ctx->smp_ev)
-    if (hipEventCreate(&e) != hipSuccess) {
-      e = nullptr;
-      sample_release(ctx);
-      return set_error(ctx, SGN_EDEVICE, "hipEventCreate failed (sgn_sample_enable)");
-    }
+  if (!ctx->smp_ev.make()) {
+    sample_release(ctx);
+    return set_error(ctx, SGN_EDEVICE, "hipEventCreate failed (sgn_sample_enable)");
+  }
   ctx->smp_cap = row_capacity;
   if (int rc = smp_rebase(ctx, "sgn_sample_enable")) {
     sample_release(ctx);
@@ -358,14 +304,14 @@ int sgn_sample(sgn_ctx* ctx, sgn_sample_info* out) {
                                           ", baseline of round " + std::to_string(ctx->smp_base_rounds) + "): sgn_sample_rebase first");
   SGN_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t nH = ctx->S.nH, nW = (nH + 63) / 64;
-  const SmpLay L = smp_lay(nH);
+  const SmpLay L = smp_lay(nW);
   char* m = (char*)ctx->smp_scratch;
   SmpHdr* d_hdr = (SmpHdr*)(m + L.hdr);
   uint32_t* d_cnt = (uint32_t*)(m + L.cnt);
   uint32_t* d_off = (uint32_t*)(m + L.off);
   const SmpArgs a = smp_args(ctx);
   hipStream_t st = ctx->stream;
-  hipEvent_t* ev = ctx->smp_ev;
+  const ReportEvents<8>& ev = ctx->smp_ev;
   const uint32_t blocks = (nH + kSmpThreads - 1) / kSmpThreads;
   SmpHdr h{};
   if (nH) {
@@ -375,9 +321,7 @@ int sgn_sample(sgn_ctx* ctx, sgn_sample_info* out) {
     (void)hipEventRecord(ev[1], st);
     hipLaunchKernelGGL(k_sample_scan, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t*)d_cnt, nW, d_off, d_hdr);
     (void)hipEventRecord(ev[2], st);
-    SGN_HIP(ctx, hipGetLastError());
-    SGN_HIP(ctx, hipMemcpyAsync(&h, d_hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-    SGN_HIP(ctx, hipStreamSynchronize(st));
+    if (int rc = read_header(ctx, d_hdr, &h)) return rc;
     if (h.err) return smp_bad(ctx, "sgn_sample", h);
     if (h.rows > nH) return set_error(ctx, SGN_EDEVICE, "sgn_sample: the wave counts add up to more rows than hosts");
   }
@@ -390,9 +334,7 @@ int sgn_sample(sgn_ctx* ctx, sgn_sample_info* out) {
     hipLaunchKernelGGL(k_sample_scatter, dim3(blocks), dim3(kSmpThreads), 0, st, a, (const uint32_t*)d_off,
                        (sgn_sample_row*)ctx->smp_rows, ctx->smp_pending, ctx->smp_cap, (uint32_t)ctx->smp_index, d_hdr);
     (void)hipEventRecord(ev[4], st);
-    SGN_HIP(ctx, hipGetLastError());
-    SGN_HIP(ctx, hipMemcpyAsync(&h, d_hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-    SGN_HIP(ctx, hipStreamSynchronize(st));
+    if (int rc = read_header(ctx, d_hdr, &h)) return rc;
     if (h.err) return smp_bad(ctx, "sgn_sample", h);
   }
   sgn_sample_info info{};
@@ -412,10 +354,9 @@ int sgn_sample(sgn_ctx* ctx, sgn_sample_info* out) {
   const double copy_ms = T.copy_ms;  // (of the last take)
   T = sgn_sample_timing{};
   T.copy_ms = copy_ms;
-  float ms = 0;
-  if (nH && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) T.kernel_ms[0] = ms;
-  if (nH && hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) T.kernel_ms[1] = ms;
-  if (rows && hipEventElapsedTime(&ms, ev[3], ev[4]) == hipSuccess) T.kernel_ms[2] = ms;
+  if (nH) T.kernel_ms[0] = elapsed_ms(ev[0], ev[1]);
+  if (nH) T.kernel_ms[1] = elapsed_ms(ev[1], ev[2]);
+  if (rows) T.kernel_ms[2] = elapsed_ms(ev[3], ev[4]);
   T.hosts = nH;
   T.rows = rows;
   T.total_ms = ms_since(t_begin);
@@ -453,8 +394,7 @@ int sgn_sample_take(sgn_ctx* ctx, sgn_sample_row* out, uint64_t cap, uint64_t* n
     SGN_HIP(ctx, hipMemcpyAsync(out, ctx->smp_rows, n * sizeof(sgn_sample_row), hipMemcpyDeviceToHost, st));
     (void)hipEventRecord(ctx->smp_ev[6], st);
     SGN_HIP(ctx, hipStreamSynchronize(st));
-    float ms = 0;
-    ctx->smp_timing.copy_ms = hipEventElapsedTime(&ms, ctx->smp_ev[5], ctx->smp_ev[6]) == hipSuccess ? ms : 0;
+    ctx->smp_timing.copy_ms = elapsed_ms(ctx->smp_ev[5], ctx->smp_ev[6]);
   } else {
     ctx->smp_timing.copy_ms = 0;
   }
@@ -470,6 +410,34 @@ int sgn_sample_timing_get(sgn_ctx* ctx, sgn_sample_timing* out) {
   if (!ctx || !out) return ctx ? set_error(ctx, SGN_EINVAL, "sgn_sample_timing_get: null argument") : SGN_EINVAL;
   if (int rc = smp_precheck(ctx, "sgn_sample_timing_get")) return rc;
   *out = ctx->smp_timing;
+  return 0;
+}
+
+// Test hook: k_sample_scan on the caller's counts (no simulation needed).
+int sgn_selftest_report_scan(sgn_ctx* ctx, const uint32_t* counts, uint32_t n, uint32_t* off_out, uint64_t* total_out) {
+  if (!ctx || !total_out || (n && (!counts || !off_out)))
+    return ctx ? set_error(ctx, SGN_EINVAL, "sgn_selftest_report_scan: null argument") : SGN_EINVAL;
+  SGN_HIP(ctx, hipSetDevice(ctx->device));
+  const SmpLay L = smp_lay(std::max<uint32_t>(n, 1u));
+  char* m = nullptr;
+  SGN_HIP(ctx, hipMalloc(&m, L.bytes));
+  SmpHdr* d_hdr = (SmpHdr*)(m + L.hdr);
+  uint32_t* d_cnt = (uint32_t*)(m + L.cnt);
+  uint32_t* d_off = (uint32_t*)(m + L.off);
+  hipStream_t st = ctx->stream;
+  SmpHdr h{};
+  hipError_t e = hipMemsetAsync(d_hdr, 0, sizeof(SmpHdr), st);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(d_cnt, counts, (size_t)n * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_sample_scan, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t*)d_cnt, n, d_off, d_hdr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && n) e = hipMemcpyAsync(off_out, d_off, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h, d_hdr, sizeof(h), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(m);
+  if (e != hipSuccess) return hip_fail(ctx, e, "report scan selftest");
+  *total_out = h.rows;
   return 0;
 }
 

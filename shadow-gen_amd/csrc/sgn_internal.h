@@ -730,6 +730,35 @@ constexpr uint32_t kXBin = 32;
 // counts itself in with a device atomic on one word
 constexpr uint32_t kImportBlocks = 16;
 
+// The HIP events a report times its launches with (report_common.h has the rest of what the reports
+// share; this is here because sgn_ctx holds two). make() creates all N or none.
+namespace report {
+template <unsigned N>
+struct ReportEvents {
+  hipEvent_t ev[N] = {};
+  ReportEvents() = default;
+  ReportEvents(const ReportEvents&) = delete;
+  ReportEvents& operator=(const ReportEvents&) = delete;
+  ~ReportEvents() { release(); }
+  bool make() {
+    for (hipEvent_t& e : ev)
+      if (hipEventCreate(&e) != hipSuccess) {
+        e = nullptr;
+        release();
+        return false;
+      }
+    return true;
+  }
+  void release() {
+    for (hipEvent_t& e : ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+  hipEvent_t operator[](unsigned i) const { return ev[i]; }
+};
+}  // namespace report
+
 }  // namespace sgn
 
 struct sgn_ctx;
@@ -811,14 +840,14 @@ struct sgn_ctx {
   uint64_t smp_index = 0, smp_base_rounds = 0;
   bool smp_stale = false;
   std::vector<sgn_sample_info> smp_infos;
-  hipEvent_t smp_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  sgn::report::ReportEvents<8> smp_ev;
   sgn_sample_timing smp_timing{};         // of the last sgn_sample (copy_ms: of the last sgn_sample_take)
   // the backlog report (backlog.hip): its device scratch (header, per-slot calendar lines, per-wave
   // words, rows), the pinned staging buffer of its copies, and the HIP events of the timing.
   // Allocated by the first sgn_backlog of a simulation, dropped by sgn_sim_init (backlog_release).
   void* bk_scratch = nullptr;
   void* bk_stage = nullptr;
-  hipEvent_t bk_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  sgn::report::ReportEvents<8> bk_ev;
   bool bk_timed = false;                  // bk_timing is of a sgn_backlog of this simulation
   sgn_backlog_timing bk_timing{};
   uint64_t drain_cap = 0;                 // sgn_drain_enable (EXTERNAL traffic)

@@ -18,9 +18,11 @@
 
 #include "snapshot_priv.h"
 // (after the HIP runtime header above: its function qualifiers)
+#include "report_common.h"  // (ms_since)
 #include "sgn_workload.h"
 
 using namespace sgn;
+using sgn::report::ms_since;
 
 // ---- device side ----------------------------------------------------------------------------
 namespace {
@@ -335,8 +337,6 @@ struct Events {
       if (e) (void)hipEventDestroy(e);
   }
 };
-
-double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
 // the file functions' streams
 int file_write(void* user, const void* data, size_t len) { return std::fwrite(data, 1, len, (FILE*)user) == len ? 0 : 1; }

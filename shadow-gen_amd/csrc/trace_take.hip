@@ -32,9 +32,10 @@
 #include <cstring>
 #include <string>
 
-#include "sgn_internal.h"
+#include "report_common.h"
 
 using namespace sgn;
+using namespace sgn::report;  // the scan (kScanTile = 1024 hosts a tile), report_fail, the host scaffolding
 
 // ---- device side ----------------------------------------------------------------------------
 namespace {
@@ -42,8 +43,6 @@ namespace {
 constexpr uint32_t kTakeThreads = 256;                   // k_take_count, k_take_scatter: 64 records a pass
 constexpr uint32_t kTakeRecs = kTakeThreads / 4;
 constexpr uint32_t kTakeMaxBlocks = 2048;                // grid-stride above that
-constexpr uint32_t kScanThreads = 256, kScanPer = 4;     // k_take_scan: one workgroup, tiles of 1024 hosts
-constexpr uint32_t kScanTile = kScanThreads * kScanPer;
 constexpr uint32_t kRecWords = sizeof(sgn_trace_rec) / 8;
 static_assert(sizeof(sgn_trace_rec) == 56 && alignof(sgn_trace_rec) == 8, "a record is seven 8-byte words");
 static_assert(offsetof(sgn_trace_rec, host) == 4 && offsetof(sgn_trace_rec, seq) == 40, "word 0 holds the host, word 5 the seq");
@@ -60,8 +59,6 @@ struct __attribute__((aligned(16))) TakeHdr {
   uint64_t pad[5];
 };
 static_assert(sizeof(TakeHdr) == 64, "");
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 // lane k (0..3) of the four that read record i: one or two of its words, w[0..nw), from word wi on
 struct Piece {
@@ -96,9 +93,6 @@ __device__ __forceinline__ void piece_key(const Piece& q, uint64_t i, uint32_t* 
   *host = (uint32_t)(w0 >> 32);
   *seq = (i & 1) ? so : se;
 }
-__device__ __forceinline__ void take_fail(TakeHdr* hdr, uint32_t bit, uint32_t host) {
-  if ((atomicOr(&hdr->err, bit) & bit) == 0) hdr->err_host = host;
-}
 
 // 1. per owned host (index HostId - lo): records, smallest and largest seq.
 // cnt and mx start at 0, mn at all ones (the host code's memsets).
@@ -117,7 +111,7 @@ __global__ __launch_bounds__(kTakeThreads) void k_take_count(const sgn_trace_rec
     if (!valid || k != 0) continue;
     const uint32_t idx = host - lo;
     if (idx >= nH) {
-      take_fail(hdr, TAKE_EHOST, host);
+      report_fail(&hdr->err, &hdr->err_host, TAKE_EHOST, host);
       continue;
     }
     atomicAdd(&cnt[idx], 1ull);
@@ -126,81 +120,35 @@ __global__ __launch_bounds__(kTakeThreads) void k_take_count(const sgn_trace_rec
   }
 }
 
-// 2. one workgroup walks the hosts in tiles of kScanTile, carrying the running totals: off[h] =
-// records of the hosts before h, and a span for every host with records (ascending HostId).
+// what k_take_scan scans: a host's records, and 1 for a host that has any
+struct TakeSum {
+  uint64_t c;
+  uint32_t s;
+};
+__device__ __forceinline__ TakeSum operator+(TakeSum a, TakeSum b) { return TakeSum{a.c + b.c, a.s + b.s}; }
+__device__ __forceinline__ TakeSum scan_shfl_up(TakeSum v, uint32_t d) { return TakeSum{__shfl_up(v.c, d), __shfl_up(v.s, d)}; }
+
+// 2. one workgroup scans (records, hosts with records) over the hosts (tiled_scan): off[h] = records
+// of the hosts before h, and a span for every host with records (ascending HostId).
 __global__ __launch_bounds__(kScanThreads) void k_take_scan(const unsigned long long* __restrict__ cnt,
                                                             const unsigned long long* __restrict__ mn,
                                                             const unsigned long long* __restrict__ mx, uint32_t lo, uint32_t nH,
                                                             uint64_t* __restrict__ off, sgn_trace_span* __restrict__ spans,
                                                             uint64_t span_cap, TakeHdr* __restrict__ hdr) {
-  __shared__ uint64_t ws_c[kScanThreads / 64];
-  __shared__ uint32_t ws_s[kScanThreads / 64];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint64_t carry_c = 0;  // (the same in every thread)
-  uint64_t carry_s = 0;
-  for (uint32_t t0 = 0; t0 < nH; t0 += kScanTile) {
-    const uint32_t h0 = t0 + threadIdx.x * kScanPer;
-    uint64_t c[kScanPer];
-    uint64_t tc = 0;
-    uint32_t ts = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kScanPer; j++) {
-      const uint32_t h = h0 + j;
-      c[j] = h < nH ? cnt[h] : 0;
-      if (c[j]) {
-        if (mx[h] - mn[h] + 1 != c[j]) take_fail(hdr, TAKE_ESEQ, lo + h);
-        ts++;
-      }
-      tc += c[j];
-    }
-    // inclusive scan of (tc, ts) over the wave, then over the workgroup's waves
-    uint64_t ic = tc;
-    uint32_t is = ts;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint64_t vc = __shfl_up(ic, d);
-      const uint32_t vs = __shfl_up(is, d);
-      if (lane >= d) {
-        ic += vc;
-        is += vs;
-      }
-    }
-    if (lane == 63) {
-      ws_c[w] = ic;
-      ws_s[w] = is;
-    }
-    __syncthreads();
-    uint64_t ec = carry_c, tot_c = 0;
-    uint64_t es = carry_s, tot_s = 0;
-#pragma unroll
-    for (uint32_t v = 0; v < kScanThreads / 64; v++) {
-      if (v < w) {
-        ec += ws_c[v];
-        es += ws_s[v];
-      }
-      tot_c += ws_c[v];
-      tot_s += ws_s[v];
-    }
-    ec += ic - tc;
-    es += is - ts;
-#pragma unroll
-    for (uint32_t j = 0; j < kScanPer; j++) {
-      const uint32_t h = h0 + j;
-      if (h >= nH) break;
-      off[h] = ec;
-      if (c[j]) {
-        if (es < span_cap) spans[es] = sgn_trace_span{lo + h, 0u, ec, c[j]};
-        es++;
-      }
-      ec += c[j];
-    }
-    carry_c += tot_c;
-    carry_s += tot_s;
-    __syncthreads();  // (the next tile writes ws_*)
-  }
+  const TakeSum sum = tiled_scan<TakeSum>(
+      nH,
+      [&](uint32_t h) {
+        const uint64_t c = cnt[h];
+        if (c && mx[h] - mn[h] + 1 != c) report_fail(&hdr->err, &hdr->err_host, TAKE_ESEQ, lo + h);
+        return TakeSum{c, c ? 1u : 0u};
+      },
+      [&](uint32_t h, TakeSum before, TakeSum own) {
+        off[h] = before.c;
+        if (own.c && before.s < span_cap) spans[before.s] = sgn_trace_span{lo + h, 0u, before.c, own.c};
+      });
   if (threadIdx.x == 0) {
-    hdr->total = carry_c;
-    hdr->n_spans = carry_s;
+    hdr->total = sum.c;
+    hdr->n_spans = sum.s;
   }
 }
 
@@ -227,7 +175,7 @@ __global__ __launch_bounds__(kTakeThreads) void k_take_scatter(const sgn_trace_r
       if (d < cnt[idx]) j = off[idx] + d;
     }
     if (j >= n) {
-      if (k == 0) take_fail(hdr, TAKE_ERANGE, host);
+      if (k == 0) report_fail(&hdr->err, &hdr->err_host, TAKE_ERANGE, host);
       continue;
     }
     uint64_t* dst = staging + j * kRecWords + q.wi;
@@ -241,42 +189,23 @@ __global__ __launch_bounds__(kTakeThreads) void k_take_scatter(const sgn_trace_r
 // ---- host side ------------------------------------------------------------------------------
 namespace {
 
-inline size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 // the scratch of one take: header, per-host words, spans, the staging records
 struct TakeLay {
   size_t hdr, cnt, mx, mn, off, spans, staging, bytes;
 };
 TakeLay take_lay(uint32_t nH, uint64_t n_spans, uint64_t n) {
+  ScratchLay s;
   TakeLay l;
-  l.hdr = 0;
-  l.cnt = sizeof(TakeHdr);
-  l.mx = l.cnt + (size_t)nH * 8;  // (cnt and mx adjacent: one memset to zero)
-  l.mn = l.mx + (size_t)nH * 8;
-  l.off = l.mn + (size_t)nH * 8;
-  l.spans = up16(l.off + (size_t)nH * 8);
-  l.staging = up16(l.spans + (size_t)n_spans * sizeof(sgn_trace_span));
-  l.bytes = l.staging + (size_t)n * sizeof(sgn_trace_rec);
+  l.hdr = s.take(sizeof(TakeHdr), 16);
+  l.cnt = s.take((size_t)nH * 8, 8);
+  l.mx = s.take((size_t)nH * 8, 8);  // (header, cnt and mx adjacent: one memset to zero)
+  l.mn = s.take((size_t)nH * 8, 8);
+  l.off = s.take((size_t)nH * 8, 8);
+  l.spans = s.take((size_t)n_spans * sizeof(sgn_trace_span), 16);
+  l.staging = s.take((size_t)n * sizeof(sgn_trace_rec), 16);
+  l.bytes = s.bytes;
   return l;
 }
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-struct TakeEvents {
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool make() {
-    for (hipEvent_t& e : ev)
-      if (hipEventCreate(&e) != hipSuccess) return false;
-    return true;
-  }
-  ~TakeEvents() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
 int take_precheck(sgn_ctx* ctx, const char* what) {
   if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
   if (!ctx->trace_buf) return set_error(ctx, SGN_ESTATE, std::string(what) + ": the simulation keeps no trace (sgn_trace_enable)");
@@ -357,24 +286,22 @@ int sgn_trace_take(sgn_ctx* ctx, sgn_trace_rec* out, uint64_t cap, uint64_t* n_o
   uint64_t* d_off = (uint64_t*)(m + L.off);
   sgn_trace_span* d_spans = (sgn_trace_span*)(m + L.spans);
   uint64_t* d_staging = (uint64_t*)(m + L.staging);
-  TakeEvents E;
+  ReportEvents<6> E;  // (created per take and destroyed on every way out)
   if (!E.make()) return set_error(ctx, SGN_EDEVICE, "hipEventCreate failed (sgn_trace_take)");
   hipStream_t st = ctx->stream;
   const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTakeMaxBlocks, (n + kTakeRecs - 1) / kTakeRecs);
 
   SGN_HIP(ctx, hipMemsetAsync(m + L.hdr, 0, L.mn - L.hdr, st));  // header, cnt, mx
   SGN_HIP(ctx, hipMemsetAsync(d_mn, 0xFF, (size_t)nH * 8, st));
-  (void)hipEventRecord(E.ev[0], st);
+  (void)hipEventRecord(E[0], st);
   hipLaunchKernelGGL(k_take_count, dim3(blocks), dim3(kTakeThreads), 0, st, (const sgn_trace_rec*)ctx->trace_buf, n, S.lo, nH,
                      d_cnt, d_mn, d_mx, d_hdr);
-  (void)hipEventRecord(E.ev[1], st);
+  (void)hipEventRecord(E[1], st);
   hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(kScanThreads), 0, st, (const unsigned long long*)d_cnt,
                      (const unsigned long long*)d_mn, (const unsigned long long*)d_mx, S.lo, nH, d_off, d_spans, sp_cap, d_hdr);
-  (void)hipEventRecord(E.ev[2], st);
-  SGN_HIP(ctx, hipGetLastError());
+  (void)hipEventRecord(E[2], st);
   TakeHdr h{};
-  SGN_HIP(ctx, hipMemcpyAsync(&h, d_hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-  SGN_HIP(ctx, hipStreamSynchronize(st));
+  if (int rc = read_header(ctx, d_hdr, &h)) return rc;
   auto bad = [&](const TakeHdr& x) {
     const char* why = x.err & TAKE_EHOST  ? "a record of a host this shard does not own: host "
                       : x.err & TAKE_ESEQ ? "the pending records do not carry consecutive seq: host "
@@ -391,29 +318,26 @@ int sgn_trace_take(sgn_ctx* ctx, sgn_trace_rec* out, uint64_t cap, uint64_t* n_o
     return set_error(ctx, SGN_ERANGE, "sgn_trace_take: " + std::to_string(n) + " records of " + std::to_string(h.n_spans) +
                                           " hosts are pending, the caller's arrays are smaller (nothing was taken)");
   }
-  (void)hipEventRecord(E.ev[3], st);
+  (void)hipEventRecord(E[3], st);
   hipLaunchKernelGGL(k_take_scatter, dim3(blocks), dim3(kTakeThreads), 0, st, (const sgn_trace_rec*)ctx->trace_buf, n, S.lo, nH,
                      (const unsigned long long*)d_cnt, (const unsigned long long*)d_mn, (const uint64_t*)d_off, d_staging, d_hdr);
-  (void)hipEventRecord(E.ev[4], st);
-  SGN_HIP(ctx, hipGetLastError());
-  SGN_HIP(ctx, hipMemcpyAsync(&h, d_hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-  SGN_HIP(ctx, hipStreamSynchronize(st));
+  (void)hipEventRecord(E[4], st);
+  if (int rc = read_header(ctx, d_hdr, &h)) return rc;
   if (h.err) return bad(h);
   SGN_HIP(ctx, hipMemcpyAsync(out, d_staging, n * sizeof(sgn_trace_rec), hipMemcpyDeviceToHost, st));
   if (spans && h.n_spans)
     SGN_HIP(ctx, hipMemcpyAsync(spans, d_spans, h.n_spans * sizeof(sgn_trace_span), hipMemcpyDeviceToHost, st));
-  (void)hipEventRecord(E.ev[5], st);
+  (void)hipEventRecord(E[5], st);
   SGN_HIP(ctx, hipStreamSynchronize(st));
   // the buffer is empty: the next record goes to its start
   if (int rc = trace_view_set(ctx, tn)) return rc;
   *n_out = n;
   if (n_spans) *n_spans = h.n_spans;
   sgn_trace_take_timing& T = ctx->take_timing;
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, E.ev[0], E.ev[1]) == hipSuccess) T.kernel_ms[0] = ms;
-  if (hipEventElapsedTime(&ms, E.ev[1], E.ev[2]) == hipSuccess) T.kernel_ms[1] = ms;
-  if (hipEventElapsedTime(&ms, E.ev[3], E.ev[4]) == hipSuccess) T.kernel_ms[2] = ms;
-  if (hipEventElapsedTime(&ms, E.ev[4], E.ev[5]) == hipSuccess) T.copy_ms = ms;
+  T.kernel_ms[0] = elapsed_ms(E[0], E[1]);
+  T.kernel_ms[1] = elapsed_ms(E[1], E[2]);
+  T.kernel_ms[2] = elapsed_ms(E[3], E[4]);
+  T.copy_ms = elapsed_ms(E[4], E[5]);
   T.records = n;
   T.hosts = h.n_spans;
   T.total_ms = ms_since(t_begin);

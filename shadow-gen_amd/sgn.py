@@ -360,6 +360,7 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         "sgn_trace_pcap": (C.c_int64, [C.POINTER(TraceRec), C.c_uint64, C.c_uint32, u32p, C.c_uint32,
                                        C.c_char_p, C.c_uint32]),
         "sgn_selftest_codel_law": (C.c_int, [vp, C.c_uint64, u64p]),
+        "sgn_selftest_report_scan": (C.c_int, [vp, u32p, C.c_uint32, u32p, u64p]),
         "sgn_debug_stamps": (C.c_int, [vp, u64p, C.c_uint64, u64p]),
         "sgn_debug_rounds": (C.c_int, [vp, u64p]),
         "sgn_debug_rounds_x": (C.c_int, [vp, u64p]),
