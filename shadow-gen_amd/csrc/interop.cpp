@@ -223,7 +223,7 @@ int sgn_engine_info_get(sgn_ctx* ctx, sgn_engine_info* out) {
   SGN_HIP(ctx, hipStreamSynchronize(ctx->stream));
   SGN_HIP(ctx, hipMemcpy(ctx->h_ctrl, (const void*)ctx->S.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
   const Ctrl& c = *ctx->h_ctrl;
-  out->codel_page_allocs = ctx->codel_allocs_before + c.pg_alloc;
+  out->codel_page_allocs = ctx->counters.codel_allocs_before + c.pg_alloc;
   out->codel_pages_free = c.pg_tail >= c.pg_alloc ? c.pg_tail - c.pg_alloc : 0;
   std::vector<HostRec> recs;
   if (int e = read_recs(ctx, 0, ctx->S.nH, &recs)) return e;
@@ -238,12 +238,12 @@ int sgn_engine_info_get(sgn_ctx* ctx, sgn_engine_info* out) {
   out->compute_units = (uint64_t)ncu;
   out->bucket_min_lds = ctx->S.agg_bmin;
   out->lds_per_cu = ctx->lds_per_cu;
-  out->codel_pool_grows = ctx->codel_grows;
-  out->calendar_grows = ctx->cal_grows;
-  out->calendar_spill_runs = ctx->cal_spill_runs;
+  out->codel_pool_grows = ctx->counters.codel_grows;
+  out->calendar_grows = ctx->counters.cal_grows;
+  out->calendar_spill_runs = ctx->counters.cal_spill_runs;
   out->exchange_slot_grows = ctx->xslot_grows;
-  out->rounds_held = ctx->rounds_held;
-  out->slab_extensions = ctx->ext_slabs;
+  out->rounds_held = ctx->counters.rounds_held;
+  out->slab_extensions = ctx->counters.ext_slabs;
   out->slab_extension_runs = ctx->S.ext_total;
   {
     const size_t G = ctx->S.G;
@@ -254,7 +254,7 @@ int sgn_engine_info_get(sgn_ctx* ctx, sgn_engine_info* out) {
     out->big_slab_pieces = t;
   }
   out->spill_area_runs = ctx->S.spill_cap;
-  out->spill_area_grows = ctx->spill_grows;
+  out->spill_area_grows = ctx->counters.spill_grows;
   out->exchange_mode = ctx->nranks > 1 ? ctx->x_mode : 0;
   out->inbox_slot_runs = ctx->nranks > 1 ? ctx->S.xislot : 0;
   out->inbox_grows = ctx->x_grows;

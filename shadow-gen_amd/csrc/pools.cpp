@@ -125,18 +125,18 @@ int relayout_calendar(sgn_ctx* ctx) {
     if (S.ext) dev_free(ctx, (void*)S.ext, n_slabs * 8);
     dev_free(ctx, cur, (n_slabs + 1) * 4);
     if (dhot) dev_free(ctx, dhot, hot_old.size() * 8);
-    if (cap != S.CAP) ctx->cal_grows++;
+    if (cap != S.CAP) ctx->counters.cal_grows++;
     S.pool = (decltype(S.pool))np;
     S.CAP = cap;
     S.ext = (decltype(S.ext))nxt;
     S.ext_pool = (decltype(S.ext_pool))nep;
     S.ext_total = etot;
     ctx->h_ext = etot ? next : std::vector<uint64_t>();
-    ctx->ext_slabs = nhot;
+    ctx->counters.ext_slabs = nhot;
     S.gspec = std::min<uint32_t>(S.gspec, S.CAP);
     size_round_kernels(ctx, S);
   }
-  ctx->cal_spill_runs += nsp;
+  ctx->counters.cal_spill_runs += nsp;
   // the spill area: emptied; grown when this round used more than a quarter of it
   if (nsp > S.spill_cap / 4) {
     const uint64_t ncap = std::min<uint64_t>(1ULL << 30, std::max<uint64_t>(2 * S.spill_cap, 4 * nsp));
@@ -148,7 +148,7 @@ int relayout_calendar(sgn_ctx* ctx) {
       S.spill = (decltype(S.spill))sp;
       S.spill_idx = (decltype(S.spill_idx))si;
       S.spill_cap = ncap;
-      ctx->spill_grows++;
+      ctx->counters.spill_grows++;
     } else {  // (the area as it was still works)
       if (sp) dev_free(ctx, sp, ncap * sizeof(EvRec));
       if (si) dev_free(ctx, si, ncap * 4);
@@ -205,11 +205,11 @@ int grow_codel(sgn_ctx* ctx, uint64_t extra) {
   S.cq_free = (decltype(S.cq_free))nf;
   S.cq_pages = (uint32_t)P2;
   S.div_cq.init(P2);
-  ctx->codel_allocs_before += c.pg_alloc;
+  ctx->counters.codel_allocs_before += c.pg_alloc;
   c.pg_alloc = 0;
   c.pg_tail = c.pg_avail = nfree;
   SGN_HIP(ctx, hipMemcpy((char*)S.ctrl + offsetof(Ctrl, pg_alloc), &c.pg_alloc, 3 * 8, hipMemcpyHostToDevice));
-  ctx->codel_grows++;
+  ctx->counters.codel_grows++;
   return upload_sim(ctx);
 }
 
@@ -276,7 +276,7 @@ int resolve_hold(sgn_ctx* ctx) {
   // and alone it grows nothing — the run goes on exactly as one without the pause would)
   if ((c.hold & ~HOLD_PAUSE) && free < need && (rc = grow_codel(ctx, need - free))) return rc;
   if (c.hold & HOLD_PAUSE) ctx->paused = true;
-  if (c.hold & ~HOLD_PAUSE) ctx->rounds_held++;
+  if (c.hold & ~HOLD_PAUSE) ctx->counters.rounds_held++;
   c.hold = 0;
   c.hold_need = 0;
   SGN_HIP(ctx, hipMemcpy((char*)ctx->S.ctrl + offsetof(Ctrl, hold), &c.hold, 4, hipMemcpyHostToDevice));

@@ -29,7 +29,7 @@ constexpr uint64_t kTimeEvery = 8;        // per-round launches: one timed in kT
 const void* execute_fn(const DevSim& S) { return round_kernels(S.tkind).execute[S.trace_on ? 1 : 0]; }
 const void* rounds_fn(const DevSim& S, bool big) { return round_kernels(S.tkind).rounds[S.stamps ? 1 : 0][big ? 1 : 0]; }
 // the persistent kernel with the big-slab path only while a slab can hold more than CAP runs
-bool rounds_big(const sgn_ctx* ctx) { return ctx->ext_slabs > 0; }
+bool rounds_big(const sgn_ctx* ctx) { return ctx->counters.ext_slabs > 0; }
 // the census verdict of the last persistent launch: 1 resident, 2 not (0: none recorded)
 uint32_t census_verdict(const sgn_ctx* ctx, uint32_t epoch) {
   const uint32_t v = ctx->h_ctrl->res_verdict;
@@ -200,7 +200,7 @@ int launch_round(sgn_ctx* ctx) {
     // single shard: k_execute's last wave runs the round edge (finalize_fused)
   }
   SGN_HIP(ctx, hipGetLastError());
-  ctx->rounds_enqueued++;
+  ctx->counters.rounds_enqueued++;
   return 0;
 }
 

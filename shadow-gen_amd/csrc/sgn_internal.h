@@ -759,6 +759,19 @@ struct ReportEvents {
 };
 }  // namespace report
 
+// The host-side counters of a simulation, in the order a snapshot file's header carries them (every
+// field a u64: no padding). sgn_sim_init zeroes them, a snapshot saves them, a restore rewinds them
+// and a snapshot file holds them, each as ONE assignment of the struct: a counter added here is in
+// all four. (xslot_grows is not here: the exchange layer is not rewound.)
+struct SimCounters {
+  uint64_t rounds_enqueued;
+  // pool growth (a held round, then a larger pool): counts for sgn_engine_info
+  uint64_t codel_grows, cal_grows, cal_spill_runs;
+  uint64_t ext_slabs, spill_grows;  // slabs with an extension; spill-area growths
+  uint64_t rounds_held;
+  uint64_t codel_allocs_before;  // page allocations before the last pool growth (its ring restarts)
+};
+
 }  // namespace sgn
 
 struct sgn_ctx;
@@ -868,7 +881,7 @@ struct sgn_ctx {
   uint64_t rng_stage_cap = 0;
   std::mutex stage_mu;
   uint64_t stage_cap = 0;
-  uint64_t rounds_enqueued = 0;
+  sgn::SimCounters counters{};  // rounds enqueued, pool growth: what a snapshot rewinds
 
   // multi-GPU
   void* comm = nullptr;  // ncclComm_t
@@ -905,12 +918,9 @@ struct sgn_ctx {
   uint32_t res_epoch = 0, res_base = 0;  // persistent launches so far / census arrivals so far
   bool persist_off = false;        // ... since sim_init: per-round launches from then on
   uint32_t lds_per_cu = 0;         // LDS bytes per CU (device attribute; the residency model)
-  // pool growth (a held round, then a larger pool): counts for sgn_engine_info
-  uint64_t codel_grows = 0, cal_grows = 0, cal_spill_runs = 0, xslot_grows = 0, rounds_held = 0;
-  uint64_t ext_slabs = 0, spill_grows = 0;  // slabs with an extension; spill-area growths
-  std::vector<uint64_t> h_ext;              // host mirror of DevSim::ext (empty: none)
+  uint64_t xslot_grows = 0;         // exchange-slot growths, for sgn_engine_info (the other counts: counters)
+  std::vector<uint64_t> h_ext;      // host mirror of DevSim::ext (empty: none)
   std::string failed;  // sticky: an operation left the device state unusable (every call fails)
-  uint64_t codel_allocs_before = 0;  // page allocations before the last pool growth (its ring restarts)
   bool capturing = false;
   // persistent multi-shard rounds (k_rounds_x): this shard's inbox (uncached device memory:
   // peers write it over xGMI), its XPeer table, peer inboxes opened from IPC handles (one shard

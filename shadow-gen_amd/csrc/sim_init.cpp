@@ -233,9 +233,8 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
   const uint32_t N = ctx->n_all;
   ctx->persist_off = false;
   ctx->res_epoch = ctx->res_base = 0;  // (the new control block's census words are zero)
-  ctx->codel_grows = ctx->cal_grows = ctx->cal_spill_runs = ctx->xslot_grows = ctx->rounds_held = 0;
-  ctx->codel_allocs_before = 0;
-  ctx->ext_slabs = ctx->spill_grows = 0;
+  ctx->counters = {};
+  ctx->xslot_grows = 0;
   ctx->h_ext.clear();
   ctx->failed.clear();
   S.n_all = N;
@@ -691,7 +690,6 @@ int sgn_sim_init(sgn_ctx* ctx, const sgn_sim_config* cfg, const sgn_traffic* tr)
   ctx->sim_tr = *tr;
   ctx->sim_tr.server_hosts = nullptr;
   ctx->paused = false;
-  ctx->rounds_enqueued = 0;
   for (int i = 0; i < K_NUM; i++) ctx->kt[i] = {kKernelNames[i], 0, 0.0, 0};
   return 0;
 }

@@ -11,6 +11,8 @@
 #include <cstring>
 
 #include "snapshot_priv.h"
+// (after the HIP runtime header above: its function qualifiers)
+#include "report_common.h"  // (elapsed_ms)
 
 using namespace sgn;
 
@@ -183,26 +185,30 @@ using Buf = sgn_snapshot::Buf;
 // state; the round buffers (rb_min, rb_keep, rb_cnt, rb_occ, fin_*) are idle at a round edge —
 // the per-round finalize exchanges them back to their reset values and a persistent launch resets
 // them itself before its census; rb_free is three words of that kind, saved anyway.
-std::vector<std::pair<void*, size_t>> sgn::state_buffers(const DevSim& S) {
+std::vector<StateBuf> sgn::state_buffers(const DevSim& S) {
   const size_t nH = S.nH, n_slabs = (size_t)(S.NB + 1) * S.G;
-  std::vector<std::pair<void*, size_t>> v;
-  v.push_back({(void*)S.hrec, nH * sizeof(HostRec)});
-  v.push_back({(void*)S.htile, S.htile ? (nH + 63) / 64 * 8 * 64 * 16 : 0});
-  v.push_back({(void*)S.n_cnt, (size_t)N_CNT * nH * 8});
-  v.push_back({(void*)S.maxq, nH * 4});
-  v.push_back({(void*)S.nextloc, nH * 8});
-  v.push_back({(void*)S.npeer, S.npeer ? nH * 4 : 0});
-  v.push_back({(void*)S.rb_free, 3 * 8});
-  v.push_back({(void*)S.fifo, nH * (size_t)S.fifo_cap * sizeof(FifoEnt)});
-  v.push_back({(void*)S.fifo_addr, S.fifo_addr ? nH * (size_t)S.fifo_cap * 4 : 0});
-  v.push_back({(void*)S.slab_n, n_slabs * 4});
-  v.push_back({(void*)S.bucket_slab, (size_t)S.NB * 4});
-  v.push_back({(void*)S.bucket_min, (size_t)S.NB * 8});
-  v.push_back({(void*)S.w_cnt, (size_t)W_N * S.G * 8});
-  return v;
+  return {
+      {"hrec", (void*)S.hrec, nH * sizeof(HostRec)},
+      {"htile", (void*)S.htile, S.htile ? (nH + 63) / 64 * 8 * 64 * 16 : 0},
+      {"n_cnt", (void*)S.n_cnt, (size_t)N_CNT * nH * 8},
+      {"maxq", (void*)S.maxq, nH * 4},
+      {"nextloc", (void*)S.nextloc, nH * 8},
+      {"npeer", (void*)S.npeer, S.npeer ? nH * 4 : 0},
+      {"rb_free", (void*)S.rb_free, 3 * 8},
+      {"fifo", (void*)S.fifo, nH * (size_t)S.fifo_cap * sizeof(FifoEnt)},
+      {"fifo_addr", (void*)S.fifo_addr, S.fifo_addr ? nH * (size_t)S.fifo_cap * 4 : 0},
+      {"slab_n", (void*)S.slab_n, n_slabs * 4},
+      {"bucket_slab", (void*)S.bucket_slab, (size_t)S.NB * 4},
+      {"bucket_min", (void*)S.bucket_min, (size_t)S.NB * 8},
+      {"w_cnt", (void*)S.w_cnt, (size_t)W_N * S.G * 8},
+  };
 }
-const char* const sgn::kStateBufferNames[] = {"hrec",     "htile",     "n_cnt",  "maxq",        "nextloc",    "npeer", "rb_free",
-                                              "fifo",     "fifo_addr", "slab_n", "bucket_slab", "bucket_min", "w_cnt"};
+const Buf* sgn::snap_fixed(const sgn_snapshot* s, const DevSim& S, const void* p) {
+  const auto v = state_buffers(S);
+  for (size_t k = 0; k < v.size() && k < s->fixed.size(); k++)
+    if (v[k].p == p) return &s->fixed[k];
+  return nullptr;
+}
 
 bool sgn::snap_buf_alloc(Buf* b, size_t bytes) {
   b->d = nullptr;
@@ -210,14 +216,13 @@ bool sgn::snap_buf_alloc(Buf* b, size_t bytes) {
   return bytes == 0 || hipMalloc(&b->d, bytes) == hipSuccess;
 }
 void sgn::snap_release(sgn_snapshot* s) {
-  auto buf_free = [](Buf* b) {
-    if (b->d) (void)hipFree(b->d);
-    b->d = nullptr;
-    b->bytes = 0;
+  auto buf_free = [](Buf& b) {
+    if (b.d) (void)hipFree(b.d);
   };
-  for (Buf& b : s->fixed) buf_free(&b);
-  for (Buf* b : {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain, &s->packed, &s->trace})
-    buf_free(b);
+  for (Buf& b : s->fixed) buf_free(b);
+  for (Buf& b : s->pool) buf_free(b);
+  buf_free(s->packed);
+  buf_free(s->trace);
   delete s;
 }
 void sgn::snap_fill_info(sgn_snapshot* s, uint64_t n_slabs) {
@@ -227,16 +232,14 @@ void sgn::snap_fill_info(sgn_snapshot* s, uint64_t n_slabs) {
   in.window_end = s->ctrl.we;
   in.device_bytes = s->packed.bytes + s->trace.bytes;
   for (const Buf& b : s->fixed) in.device_bytes += b.bytes;
-  for (const Buf* b : {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain}) in.device_bytes += b->bytes;
+  for (const Buf& b : s->pool) in.device_bytes += b.bytes;
   in.host_bytes = sizeof(sgn_snapshot) + s->fixed.size() * sizeof(Buf) + s->handles.size() * 8 + s->submit_seq.size() * 4 +
                   s->drain_held.size() * sizeof(sgn_drain_rec) + s->h_ext.size() * 8;
   in.calendar_runs = s->runs;
   in.calendar_bytes = s->runs * sizeof(EvRec);
-  in.calendar_pool_bytes = (n_slabs * s->S.CAP + s->S.ext_total) * sizeof(EvRec);
+  in.calendar_pool_bytes = (n_slabs * s->lay.cap + s->lay.ext_total) * sizeof(EvRec);
 }
 namespace {
-inline bool buf_alloc(Buf* b, size_t bytes) { return snap_buf_alloc(b, bytes); }
-
 // the scan's scratch: off (n_slabs + 1 words, the last the total) and the tile sums
 struct Scan {
   uint64_t* off = nullptr;
@@ -309,28 +312,22 @@ int save_one(sgn_ctx* ctx, sgn_snapshot** out) {
 
   sgn_snapshot* s = new sgn_snapshot();
   Scan sc;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  report::ReportEvents<5> ev;  // around the scan, around the pack, after the copies
   auto fail = [&](int code, const std::string& msg) {
     (void)hipStreamSynchronize(st);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
     snap_release(s);
     return set_error(ctx, code, msg);
   };
   const char* oom = "device allocation failed (snapshot)";
-  for (hipEvent_t& e : ev)
-    if (hipEventCreate(&e) != hipSuccess) return fail(SGN_EDEVICE, "hipEventCreate failed (snapshot)");
+  if (!ev.make()) return fail(SGN_EDEVICE, "hipEventCreate failed (snapshot)");
   // every buffer but the packed calendar (its size is the scan's result)
   const auto src = state_buffers(S);
+  const auto pools = pool_buffers(S, layout_of(S), std::min<uint64_t>(c.spill_n, S.spill_cap),
+                                  S.drain ? std::min<uint64_t>(c.drain_n, S.drain_cap) : 0);
   s->fixed.resize(src.size());
   bool ok = sc.alloc(n_slabs);
-  for (size_t k = 0; ok && k < src.size(); k++) ok = buf_alloc(&s->fixed[k], src[k].second);
-  const size_t P = S.cq_pages;
-  const uint64_t nsp = std::min<uint64_t>(c.spill_n, S.spill_cap);
-  const uint64_t ndr = S.drain ? std::min<uint64_t>(c.drain_n, S.drain_cap) : 0;
-  ok = ok && buf_alloc(&s->codel, P * CQ_PAGE * sizeof(CodelEnt)) && buf_alloc(&s->cq_next, P * 4) &&
-       buf_alloc(&s->cq_free, P * 4) && buf_alloc(&s->spill, nsp * sizeof(EvRec)) && buf_alloc(&s->spill_idx, nsp * 4) &&
-       buf_alloc(&s->drain, ndr * sizeof(sgn_drain_rec));
+  for (size_t k = 0; ok && k < src.size(); k++) ok = snap_buf_alloc(&s->fixed[k], src[k].bytes);
+  for (size_t k = 0; ok && k < POOL_N; k++) ok = snap_buf_alloc(&s->pool[k], pools[k].bytes);
   if (!ok) return fail(SGN_ENOMEM, oom);
 
   // the scan first: the host needs its total before it can size the packed section
@@ -342,7 +339,7 @@ int save_one(sgn_ctx* ctx, sgn_snapshot** out) {
       hipStreamSynchronize(st) != hipSuccess)
     return fail(SGN_EDEVICE, "snapshot: the calendar scan failed");
   if (total > n_slabs * S.CAP + S.ext_total) return fail(SGN_ESTATE, "snapshot: calendar fill above its capacity");
-  if (!buf_alloc(&s->packed, total * sizeof(EvRec))) return fail(SGN_ENOMEM, oom);
+  if (!snap_buf_alloc(&s->packed, total * sizeof(EvRec))) return fail(SGN_ENOMEM, oom);
   s->runs = total;
 
   auto d2d = [&](Buf& b, const void* from) {
@@ -354,46 +351,27 @@ int save_one(sgn_ctx* ctx, sgn_snapshot** out) {
                       (EvRec*)s->packed.d);
   (void)hipEventRecord(ev[3], st);
   ok = hipGetLastError() == hipSuccess;
-  for (size_t k = 0; ok && k < src.size(); k++) ok = d2d(s->fixed[k], src[k].first);
-  ok = ok && d2d(s->codel, (const void*)S.codel) && d2d(s->cq_next, (const void*)S.cq_next) &&
-       d2d(s->cq_free, (const void*)S.cq_free) && d2d(s->spill, (const void*)S.spill) &&
-       d2d(s->spill_idx, (const void*)S.spill_idx) && d2d(s->drain, (const void*)S.drain);
-  hipEvent_t ev_end = nullptr;
-  ok = ok && hipEventCreate(&ev_end) == hipSuccess && hipEventRecord(ev_end, st) == hipSuccess;
+  for (size_t k = 0; ok && k < src.size(); k++) ok = d2d(s->fixed[k], src[k].p);
+  for (size_t k = 0; ok && k < POOL_N; k++) ok = d2d(s->pool[k], pools[k].p);
+  ok = ok && hipEventRecord(ev[4], st) == hipSuccess;
   ok = ok && hipStreamSynchronize(st) == hipSuccess;
-  float ms_scan = 0, ms_pack = 0, ms_rest = 0;
-  if (ok) {
-    (void)hipEventElapsedTime(&ms_scan, ev[0], ev[1]);
-    (void)hipEventElapsedTime(&ms_pack, ev[2], ev[3]);
-    (void)hipEventElapsedTime(&ms_rest, ev[3], ev_end);
-  }
-  if (ev_end) (void)hipEventDestroy(ev_end);
   if (!ok) return fail(SGN_EDEVICE, "snapshot: a device copy failed");
-  for (hipEvent_t& e : ev) {
-    (void)hipEventDestroy(e);
-    e = nullptr;
-  }
+  const double ms_scan = report::elapsed_ms(ev[0], ev[1]), ms_pack = report::elapsed_ms(ev[2], ev[3]),
+               ms_rest = report::elapsed_ms(ev[3], ev[4]);
 
   s->ctx = ctx;
   s->gen = ctx->sim_gen;
-  s->S = S;
+  s->lay = layout_of(S);
   s->ctrl = c;
-  s->rounds_enqueued = ctx->rounds_enqueued;
+  s->counters = ctx->counters;
   s->handles = ctx->handles;
   s->submit_seq = ctx->submit_seq;
   s->drain_held = ctx->drain_held;
   s->h_ext = ctx->h_ext;
-  s->codel_grows = ctx->codel_grows;
-  s->cal_grows = ctx->cal_grows;
-  s->cal_spill_runs = ctx->cal_spill_runs;
-  s->ext_slabs = ctx->ext_slabs;
-  s->spill_grows = ctx->spill_grows;
-  s->rounds_held = ctx->rounds_held;
-  s->codel_allocs_before = ctx->codel_allocs_before;
   sgn_snapshot_info& in = s->info;
   snap_fill_info(s, n_slabs);
-  in.save_ms = (double)ms_scan + (double)ms_pack + (double)ms_rest;
-  in.pack_ms = (double)ms_scan + (double)ms_pack;
+  in.save_ms = ms_scan + ms_pack + ms_rest;
+  in.pack_ms = ms_scan + ms_pack;
   ctx->snapshots.push_back(s);
   *out = s;
   return 0;
@@ -439,18 +417,15 @@ int sgn::snap_scan_total(sgn_ctx* ctx, const uint32_t* slab_n, const uint64_t* e
 }
 
 namespace {
-inline int restore_check(sgn_ctx* ctx, const sgn_snapshot* snap, const char* what, sgn_snapshot** s_out) {
-  return snap_check(ctx, snap, what, s_out);
-}
 
-// One context back to its snapshot s (checked by restore_check). shard: a shard of a sharded run
+// One context back to its snapshot s (checked by snap_check). shard: a shard of a sharded run
 // — the exchange words of the control block belong to the launch sequence and stay live.
 int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
   SGN_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   SGN_HIP(ctx, hipStreamSynchronize(st));
   DevSim& S = ctx->S;
-  const DevSim& Z = s->S;
+  const SnapLayout L = layout_of(S), Z = s->lay;
   const uint64_t n_slabs = (uint64_t)(S.NB + 1) * S.G;
   // the launch sequence's words keep their live values (below): read them now
   Ctrl live{};
@@ -458,80 +433,60 @@ int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
 
   // ---- the snapshot's pool layout: every buffer it needs that the context does not have at
   // that size is allocated before anything changes (SGN_ENOMEM leaves the context as it was)
-  const bool codel_re = S.cq_pages != Z.cq_pages, spill_re = S.spill_cap != Z.spill_cap, cap_re = S.CAP != Z.CAP;
-  const bool ext_re = ctx->h_ext != s->h_ext;
-  const size_t P = Z.cq_pages;
-  CodelEnt* n_codel = nullptr;
-  uint32_t *n_next = nullptr, *n_free = nullptr, *n_sidx = nullptr;
-  EvRec *n_spill = nullptr, *n_pool = nullptr, *n_epool = nullptr;
-  uint64_t* n_ext = nullptr;
+  const bool cap_re = L.cap != Z.cap, ext_re = ctx->h_ext != s->h_ext;
+  // the buffers to replace: a growing pool by its index, then the calendar's three
+  enum { ST_POOL = POOL_N, ST_EXT_POOL, ST_EXT, ST_N };
+  struct Staged {
+    bool on = false;        // replaced ...
+    void* fresh = nullptr;  // ... by this one (null: by none — a layout without extensions)
+    size_t bytes = 0;
+    void* old = nullptr;
+    size_t old_bytes = 0;
+  } staged[ST_N];
   Scan sc;
-  bool ok = sc.alloc(n_slabs);
-  if (ok && codel_re) {
-    n_codel = (CodelEnt*)dev_alloc(ctx, P * CQ_PAGE * sizeof(CodelEnt), false);
-    n_next = (uint32_t*)dev_alloc(ctx, P * 4, false);
-    n_free = (uint32_t*)dev_alloc(ctx, P * 4, false);
-    ok = n_codel && n_next && n_free;
-  }
-  if (ok && spill_re) {
-    n_spill = (EvRec*)dev_alloc(ctx, Z.spill_cap * sizeof(EvRec), false);
-    n_sidx = (uint32_t*)dev_alloc(ctx, Z.spill_cap * 4, false);
-    ok = n_spill && n_sidx;
-  }
-  if (ok && cap_re) ok = (n_pool = (EvRec*)dev_alloc(ctx, n_slabs * Z.CAP * sizeof(EvRec), false)) != nullptr;
-  if (ok && ext_re && Z.ext_total) {
-    n_epool = (EvRec*)dev_alloc(ctx, Z.ext_total * sizeof(EvRec), false);
-    n_ext = (uint64_t*)dev_alloc(ctx, n_slabs * 8, false);
-    ok = n_epool && n_ext;
+  bool ok = sc.alloc(n_slabs), relaid = false;
+  auto stage = [&](uint32_t which, void* old, size_t old_bytes, size_t bytes) {
+    Staged& g = staged[which];
+    g = {true, nullptr, bytes, old, old_bytes};
+    relaid = true;
+    if (ok && bytes) ok = (g.fresh = dev_alloc(ctx, bytes, false)) != nullptr;
+  };
+  // (the pools at their capacity, in this layout and in the snapshot's; drain has no layout scalar)
+  const auto have = pool_buffers(S, L, L.spill_cap, 0), want = pool_buffers(S, Z, Z.spill_cap, 0);
+  for (uint32_t k = 0; k < POOL_N; k++)
+    if (want[k].bytes != have[k].bytes) stage(k, have[k].p, have[k].bytes, want[k].bytes);
+  if (cap_re) stage(ST_POOL, (void*)S.pool, n_slabs * L.cap * sizeof(EvRec), n_slabs * Z.cap * sizeof(EvRec));
+  if (ext_re) {
+    stage(ST_EXT_POOL, (void*)S.ext_pool, L.ext_total * sizeof(EvRec), Z.ext_total * sizeof(EvRec));
+    stage(ST_EXT, (void*)S.ext, n_slabs * 8, Z.ext_total ? n_slabs * 8 : 0);
   }
   if (!ok) {
-    dev_free(ctx, n_codel, P * CQ_PAGE * sizeof(CodelEnt));
-    dev_free(ctx, n_next, P * 4);
-    dev_free(ctx, n_free, P * 4);
-    dev_free(ctx, n_spill, Z.spill_cap * sizeof(EvRec));
-    dev_free(ctx, n_sidx, Z.spill_cap * 4);
-    dev_free(ctx, n_pool, n_slabs * Z.CAP * sizeof(EvRec));
-    dev_free(ctx, n_epool, Z.ext_total * sizeof(EvRec));
-    dev_free(ctx, n_ext, n_slabs * 8);
+    for (const Staged& g : staged) dev_free(ctx, g.fresh, g.bytes);
     return set_error(ctx, SGN_ENOMEM, "device allocation failed (snapshot restore)");
   }
   // ---- from here the context changes: the pools the run grew since go, the saved sizes return
   ctx->ctrl_fresh = false;
   ctx->rng_held.clear();  // (CPU-held draws belong to the state being replaced)
-  if (codel_re) {
-    dev_free(ctx, (void*)S.codel, (size_t)S.cq_pages * CQ_PAGE * sizeof(CodelEnt));
-    dev_free(ctx, (void*)S.cq_next, (size_t)S.cq_pages * 4);
-    dev_free(ctx, (void*)S.cq_free, (size_t)S.cq_pages * 4);
-    S.codel = (decltype(S.codel))n_codel;
-    S.cq_next = (decltype(S.cq_next))n_next;
-    S.cq_free = (decltype(S.cq_free))n_free;
-    S.cq_pages = Z.cq_pages;
-    S.div_cq.init(Z.cq_pages);
-  }
-  if (spill_re) {
-    dev_free(ctx, (void*)S.spill, S.spill_cap * sizeof(EvRec));
-    dev_free(ctx, (void*)S.spill_idx, S.spill_cap * 4);
-    S.spill = (decltype(S.spill))n_spill;
-    S.spill_idx = (decltype(S.spill_idx))n_sidx;
-    S.spill_cap = Z.spill_cap;
-  }
-  if (cap_re) {
-    dev_free(ctx, (void*)S.pool, n_slabs * S.CAP * sizeof(EvRec));
-    S.pool = (decltype(S.pool))n_pool;
-    S.CAP = Z.CAP;
-  }
+  for (const Staged& g : staged) dev_free(ctx, g.old, g.old_bytes);
+  for_each_pool(S, Z, 0, 0, [&](uint32_t k, const char*, auto& member, size_t) {
+    if (staged[k].on) member = (std::remove_reference_t<decltype(member)>)staged[k].fresh;
+  });
+  if (L.cq_pages != Z.cq_pages) S.div_cq.init(Z.cq_pages);  // (the free ring's index divides by cq_pages)
+  S.cq_pages = (uint32_t)Z.cq_pages;
+  S.spill_cap = Z.spill_cap;
+  if (cap_re) S.pool = (decltype(S.pool))staged[ST_POOL].fresh;
+  S.CAP = (uint32_t)Z.cap;
   if (ext_re) {
-    if (S.ext_pool) dev_free(ctx, (void*)S.ext_pool, S.ext_total * sizeof(EvRec));
-    if (S.ext) dev_free(ctx, (void*)S.ext, n_slabs * 8);
-    S.ext_pool = (decltype(S.ext_pool))n_epool;
+    void* n_ext = staged[ST_EXT].fresh;
+    S.ext_pool = (decltype(S.ext_pool))staged[ST_EXT_POOL].fresh;
     S.ext = (decltype(S.ext))n_ext;
     S.ext_total = Z.ext_total;
     ctx->h_ext = s->h_ext;
     if (n_ext) SGN_HIP(ctx, hipMemcpy(n_ext, s->h_ext.data(), n_slabs * 8, hipMemcpyHostToDevice));
   }
-  S.gspec = Z.gspec;
-  ctx->ext_slabs = s->ext_slabs;
-  const bool relaid = codel_re || spill_re || cap_re || ext_re;
+  S.gspec = (uint32_t)Z.gspec;
+  // (with the layout, before the copies that can fail: the big-slab path of the round kernels follows it)
+  ctx->counters.ext_slabs = s->counters.ext_slabs;
   if (cap_re) size_round_kernels(ctx, ctx->S);  // the LDS table and the persistent grid follow the slab size
   if (relaid) {
     if (int rc = upload_sim(ctx)) {
@@ -547,10 +502,10 @@ int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
     return b.bytes == 0 || hipMemcpyAsync(to, b.d, b.bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
   };
   const auto dst = state_buffers(S);
+  const auto pools = pool_buffers(S, Z, 0, 0);  // (where the pools are now: the sizes copied are the snapshot's own)
   ok = dst.size() == s->fixed.size();
-  for (size_t k = 0; ok && k < dst.size(); k++) ok = dst[k].second == s->fixed[k].bytes && d2d(dst[k].first, s->fixed[k]);
-  ok = ok && d2d((void*)S.codel, s->codel) && d2d((void*)S.cq_next, s->cq_next) && d2d((void*)S.cq_free, s->cq_free) &&
-       d2d((void*)S.spill, s->spill) && d2d((void*)S.spill_idx, s->spill_idx) && d2d((void*)S.drain, s->drain);
+  for (size_t k = 0; ok && k < dst.size(); k++) ok = dst[k].bytes == s->fixed[k].bytes && d2d(dst[k].p, s->fixed[k]);
+  for (size_t k = 0; ok && k < POOL_N; k++) ok = d2d(pools[k].p, s->pool[k]);
   // an imported snapshot brings the trace records up to its save (import checked that they fit);
   // one saved here has none: this context's trace buffer still holds them
   // The cursor of sgn_trace_take: an imported snapshot's records [b, N) go to the buffer's start
@@ -607,16 +562,10 @@ int restore_one(sgn_ctx* ctx, sgn_snapshot* s, bool shard) {
   }
   // ---- the host side of the simulation (the launch sequence — res_epoch, res_base, persist_off,
   // persist_fallbacks — the kernel-time samples and the mirror's stale word stay as they are)
-  ctx->rounds_enqueued = s->rounds_enqueued;
+  ctx->counters = s->counters;
   ctx->handles = s->handles;
   ctx->submit_seq = s->submit_seq;
   ctx->drain_held = s->drain_held;
-  ctx->codel_grows = s->codel_grows;
-  ctx->cal_grows = s->cal_grows;
-  ctx->cal_spill_runs = s->cal_spill_runs;
-  ctx->spill_grows = s->spill_grows;
-  ctx->rounds_held = s->rounds_held;
-  ctx->codel_allocs_before = s->codel_allocs_before;
   ctx->paused = false;
   return 0;
 }
@@ -635,11 +584,13 @@ int sgn_snapshot_save(sgn_ctx* ctx, sgn_snapshot** out) {
 
 int sgn_snapshot_restore(sgn_ctx* ctx, const sgn_snapshot* snap) {
   if (!ctx || !snap) return ctx ? set_error(ctx, SGN_EINVAL, "sgn_snapshot_restore: null argument") : SGN_EINVAL;
+  // (snap_check asks the first two again: a foreign snapshot and a context without a simulation are
+  // refused before a sharded context is, a stale snapshot or a failed context after)
   sgn_snapshot* s = owned(ctx, snap);
   if (!s) return set_error(ctx, SGN_EINVAL, "sgn_snapshot_restore: not a snapshot of this context");
   if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
   if (ctx->nranks > 1 || ctx->comm_local) return sharded(ctx, "sgn_snapshot_restore");
-  if (int rc = restore_check(ctx, snap, "sgn_snapshot_restore", &s)) return rc;
+  if (int rc = snap_check(ctx, snap, "sgn_snapshot_restore", &s)) return rc;
   return restore_one(ctx, s, false);
 }
 
@@ -703,7 +654,7 @@ int sgn_shards_snapshot_restore(sgn_ctx* const* ctxs, uint32_t n, sgn_snapshot* 
   int rc = 0;
   for (uint32_t i = 0; i < n && !rc; i++) {
     if (!snaps[i]) rc = set_error(sh[i], SGN_EINVAL, "sgn_shards_snapshot_restore: null snapshot");
-    else rc = restore_check(sh[i], snaps[i], "sgn_shards_snapshot_restore", &ss[i]);
+    else rc = snap_check(sh[i], snaps[i], "sgn_shards_snapshot_restore", &ss[i]);
   }
   for (uint32_t i = 1; i < n && !rc; i++)
     if (ss[i]->info.rounds != ss[0]->info.rounds || ss[i]->info.window_start != ss[0]->info.window_start)

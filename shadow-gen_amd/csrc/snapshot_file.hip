@@ -13,6 +13,7 @@
 // before anything is allocated, and nothing in it is used as an index before it has been bounded.
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 
@@ -129,11 +130,9 @@ struct FileHeader {
   uint64_t identity;
   uint64_t shard_rank, shard_count;
   uint64_t rounds, ws, we;
-  uint64_t cap, cq_pages, spill_cap, ext_total, gspec;  // the layout scalars a restore reads
-  uint64_t traced;                                      // the simulation keeps a trace
-  // the host-side counters of sgn_snapshot
-  uint64_t rounds_enqueued, codel_grows, cal_grows, cal_spill_runs, ext_slabs, spill_grows, rounds_held,
-      codel_allocs_before;
+  SnapLayout lay;        // the layout scalars a restore reads
+  uint64_t traced;       // the simulation keeps a trace
+  SimCounters counters;  // the host-side counters of sgn_snapshot
   uint64_t calendar_runs, trace_records;
   uint64_t n_sections, file_bytes;
   uint64_t reserved;  // the trace records sgn_trace_take had handed out before the export: the
@@ -141,6 +140,12 @@ struct FileHeader {
                       // word that keeps the header a multiple of 16 bytes)
 };
 static_assert(sizeof(FileHeader) % 16 == 0, "the table and the payloads start 16-byte aligned");
+// format 1, to the byte: 8 bytes of magic, then 35 u64 (a field added to SnapLayout or SimCounters
+// moves what follows it: that is a new kFormat)
+static_assert(sizeof(FileHeader) == 288 && offsetof(FileHeader, lay) == 136 && offsetof(FileHeader, traced) == 176 &&
+                  offsetof(FileHeader, counters) == 184 && offsetof(FileHeader, calendar_runs) == 248 &&
+                  offsetof(FileHeader, n_sections) == 264 && offsetof(FileHeader, reserved) == 280,
+              "FileHeader is not the header of format 1");
 struct TableEnt {
   uint64_t id, bytes, digest;
 };
@@ -148,13 +153,10 @@ struct TableEnt {
 // The sections, in file order; id = index + 1.
 enum : uint32_t {
   SEC_CTRL = 0,
-  SEC_FIXED = 1,  // one per state_buffers() entry
-  // (then, from SEC_FIXED + the number of fixed buffers:)
-  SECP_CODEL = 0, SECP_CQ_NEXT, SECP_CQ_FREE, SECP_SPILL, SECP_SPILL_IDX, SECP_DRAIN, SECP_PACKED,
-  SECP_HANDLES, SECP_SUBMIT_SEQ, SECP_DRAIN_HELD, SECP_H_EXT, SECP_TRACE, SECP_N
+  SEC_FIXED = 1,  // one per state_buffers() entry, then one per for_each_pool() entry, and from there:
+  SECT_PACKED = 0, SECT_HANDLES, SECT_SUBMIT_SEQ, SECT_DRAIN_HELD, SECT_H_EXT, SECT_TRACE, SECT_N
 };
-const char* const kPoolNames[SECP_N] = {"codel",   "cq_next",    "cq_free",    "spill", "spill_idx", "drain", "calendar",
-                                        "handles", "submit_seq", "drain_held", "h_ext", "trace"};
+const char* const kTailNames[SECT_N] = {"calendar", "handles", "submit_seq", "drain_held", "h_ext", "trace"};
 struct Sec {
   std::string name;
   bool dev = false;       // device memory (digested by k_digest), else host memory
@@ -196,20 +198,18 @@ int digest_device(sgn_ctx* ctx, std::vector<DigSec> secs, uint64_t* out, float* 
   DigSec* d_secs = (DigSec*)(d_out + out_words);
   std::vector<uint64_t> h_out(out_words);
   hipStream_t st = ctx->stream;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  report::ReportEvents<2> ev;
   bool ok = hipMemcpyAsync(d_secs, secs.data(), n * sizeof(DigSec), hipMemcpyHostToDevice, st) == hipSuccess &&
             hipMemsetAsync(d_out, 0, out_words * 8, st) == hipSuccess;
-  if (ok && ms) ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess && hipEventRecord(e0, st) == hipSuccess;
+  if (ok && ms) ok = ev.make() && hipEventRecord(ev[0], st) == hipSuccess;
   if (ok) {
     hipLaunchKernelGGL(k_digest, dim3(total), dim3(kDigThreads), 0, st, (const DigSec*)d_secs, (uint32_t)n, d_out);
     ok = hipGetLastError() == hipSuccess;
   }
-  if (ok && ms) ok = hipEventRecord(e1, st) == hipSuccess;
+  if (ok && ms) ok = hipEventRecord(ev[1], st) == hipSuccess;
   ok = ok && hipMemcpyAsync(h_out.data(), d_out, out_words * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
   ok = hipStreamSynchronize(st) == hipSuccess && ok;
-  if (ok && ms) (void)hipEventElapsedTime(ms, e0, e1);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
+  if (ok && ms) *ms = report::elapsed_ms(ev[0], ev[1]);
   (void)hipFree(d);
   if (!ok) return set_error(ctx, SGN_EDEVICE, "the digest kernel failed");
   for (size_t i = 0; i < n; i++) {
@@ -297,18 +297,20 @@ void header_base(sgn_ctx* ctx, FileHeader* h) {
   h->traced = ctx->S.trace_on ? 1 : 0;
 }
 
-// the sections of snapshot s (trace: where its trace records are, n_trace of them)
-std::vector<Sec> sections_of(const sgn_snapshot* s, const void* trace, uint64_t n_trace) {
+// the sections of snapshot s of simulation S (trace: where its trace records are, n_trace of them)
+std::vector<Sec> sections_of(const DevSim& S, const sgn_snapshot* s, const void* trace, uint64_t n_trace) {
   std::vector<Sec> v;
   v.push_back({"ctrl", false, &s->ctrl, sizeof(Ctrl)});
-  for (size_t k = 0; k < s->fixed.size(); k++) v.push_back({kStateBufferNames[k], true, s->fixed[k].d, s->fixed[k].bytes});
-  const Buf* pools[] = {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain, &s->packed};
-  for (uint32_t k = 0; k <= SECP_PACKED; k++) v.push_back({kPoolNames[k], true, pools[k]->d, pools[k]->bytes});
-  v.push_back({kPoolNames[SECP_HANDLES], false, s->handles.data(), s->handles.size() * 8});
-  v.push_back({kPoolNames[SECP_SUBMIT_SEQ], false, s->submit_seq.data(), s->submit_seq.size() * 4});
-  v.push_back({kPoolNames[SECP_DRAIN_HELD], false, s->drain_held.data(), s->drain_held.size() * sizeof(sgn_drain_rec)});
-  v.push_back({kPoolNames[SECP_H_EXT], false, s->h_ext.data(), s->h_ext.size() * 8});
-  v.push_back({kPoolNames[SECP_TRACE], true, trace, n_trace * sizeof(sgn_trace_rec)});
+  const auto fixed = state_buffers(S);  // (for the names: the bytes are the snapshot's own)
+  const auto pools = pool_buffers(S, s->lay, 0, 0);
+  for (size_t k = 0; k < s->fixed.size(); k++) v.push_back({fixed[k].name, true, s->fixed[k].d, s->fixed[k].bytes});
+  for (size_t k = 0; k < POOL_N; k++) v.push_back({pools[k].name, true, s->pool[k].d, s->pool[k].bytes});
+  v.push_back({kTailNames[SECT_PACKED], true, s->packed.d, s->packed.bytes});
+  v.push_back({kTailNames[SECT_HANDLES], false, s->handles.data(), s->handles.size() * 8});
+  v.push_back({kTailNames[SECT_SUBMIT_SEQ], false, s->submit_seq.data(), s->submit_seq.size() * 4});
+  v.push_back({kTailNames[SECT_DRAIN_HELD], false, s->drain_held.data(), s->drain_held.size() * sizeof(sgn_drain_rec)});
+  v.push_back({kTailNames[SECT_H_EXT], false, s->h_ext.data(), s->h_ext.size() * 8});
+  v.push_back({kTailNames[SECT_TRACE], true, trace, n_trace * sizeof(sgn_trace_rec)});
   return v;
 }
 
@@ -329,15 +331,6 @@ int digest_sections(sgn_ctx* ctx, const std::vector<Sec>& secs, std::vector<uint
   return 0;
 }
 
-struct Events {
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool make() { return hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess; }
-  ~Events() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
 // the file functions' streams
 int file_write(void* user, const void* data, size_t len) { return std::fwrite(data, 1, len, (FILE*)user) == len ? 0 : 1; }
 int file_read(void* user, void* data, size_t len) { return std::fread(data, 1, len, (FILE*)user) == len ? 0 : 1; }
@@ -354,7 +347,7 @@ int export_one(sgn_ctx* ctx, sgn_snapshot* s, sgn_write_fn wr, void* user, uint6
   hipStream_t st = ctx->stream;
   SGN_HIP(ctx, hipStreamSynchronize(st));
   if (int rc = stage_get(ctx)) return rc;
-  Events E;
+  report::ReportEvents<2> E;  // one per staging chunk
   if (!E.make()) return set_error(ctx, SGN_EDEVICE, "hipEventCreate failed (snapshot export)");
   FileHeader h;
   header_base(ctx, &h);
@@ -368,7 +361,7 @@ int export_one(sgn_ctx* ctx, sgn_snapshot* s, sgn_write_fn wr, void* user, uint6
   const uint64_t n_trace = s->imported ? s->trace.bytes / sizeof(sgn_trace_rec)
                                        : (ctx->trace_buf ? std::min<uint64_t>(s->ctrl.trace_n - trace_b, ctx->trace_cap) : 0);
   const void* trace = s->imported ? s->trace.d : (const void*)ctx->trace_buf;
-  const std::vector<Sec> secs = sections_of(s, trace, n_trace);
+  const std::vector<Sec> secs = sections_of(ctx->S, s, trace, n_trace);
   std::vector<uint64_t> dig;
   float dig_ms = 0;
   uint64_t dev_bytes = 0;
@@ -377,19 +370,8 @@ int export_one(sgn_ctx* ctx, sgn_snapshot* s, sgn_write_fn wr, void* user, uint6
   h.rounds = s->ctrl.rounds;
   h.ws = s->ctrl.ws;
   h.we = s->ctrl.we;
-  h.cap = s->S.CAP;
-  h.cq_pages = s->S.cq_pages;
-  h.spill_cap = s->S.spill_cap;
-  h.ext_total = s->S.ext_total;
-  h.gspec = s->S.gspec;
-  h.rounds_enqueued = s->rounds_enqueued;
-  h.codel_grows = s->codel_grows;
-  h.cal_grows = s->cal_grows;
-  h.cal_spill_runs = s->cal_spill_runs;
-  h.ext_slabs = s->ext_slabs;
-  h.spill_grows = s->spill_grows;
-  h.rounds_held = s->rounds_held;
-  h.codel_allocs_before = s->codel_allocs_before;
+  h.lay = s->lay;
+  h.counters = s->counters;
   h.calendar_runs = s->runs;
   h.trace_records = n_trace;
   h.reserved = trace_b;
@@ -518,24 +500,27 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
                                                       : "the file is of an untraced simulation and this context keeps a trace"));
   // the layout scalars: bounded before anything is sized from them
   const uint32_t cap_lim = std::max(S.CAP, max_slab_capacity(ctx, S));
-  if (h.cap == 0 || h.cap > cap_lim) return efile("slab capacity outside what this device's round kernels hold");
-  if (h.cq_pages < nH || h.cq_pages >= (1ULL << 28)) return efile("CoDel page count out of range");
-  if (h.spill_cap == 0 || h.spill_cap > (1ULL << 28)) return efile("spill area capacity out of range");
-  if (h.ext_total >= (1ULL << 40)) return efile("slab extension total out of range");
-  if (h.gspec > 64 || h.gspec > h.cap) return efile("gather width out of range");
-  if (h.calendar_runs > n_slabs * h.cap + h.ext_total) return efile("more calendar runs than the layout holds");
+  const SnapLayout& Z = h.lay;
+  if (Z.cap == 0 || Z.cap > cap_lim) return efile("slab capacity outside what this device's round kernels hold");
+  if (Z.cq_pages < nH || Z.cq_pages >= (1ULL << 28)) return efile("CoDel page count out of range");
+  if (Z.spill_cap == 0 || Z.spill_cap > (1ULL << 28)) return efile("spill area capacity out of range");
+  if (Z.ext_total >= (1ULL << 40)) return efile("slab extension total out of range");
+  if (Z.gspec > 64 || Z.gspec > Z.cap) return efile("gather width out of range");
+  if (h.calendar_runs > n_slabs * Z.cap + Z.ext_total) return efile("more calendar runs than the layout holds");
   const auto fixed = state_buffers(S);
-  if (fixed.size() <= kStateSlabN || fixed[kStateSlabN].first != (void*)S.slab_n)
-    return set_error(ctx, SGN_ESTATE, w + "state_buffers() no longer has slab_n where kStateSlabN says");
-  const size_t n_sec = SEC_FIXED + fixed.size() + SECP_N;
+  const size_t P0 = SEC_FIXED + fixed.size(), T0 = P0 + POOL_N;  // the first pool section, the first after the pools
+  const size_t n_sec = T0 + SECT_N;
   if (h.n_sections != n_sec) return efile("section count");
 
   // ---- table: every size follows from the simulation and the header
   std::vector<TableEnt> tab(n_sec);
   if (rd(user, tab.data(), n_sec * sizeof(TableEnt)) != 0) return efile("truncated in the section table");
-  const size_t P0 = SEC_FIXED + fixed.size();  // the first pool section
+  // the pools at the header's layout: nothing in the spill area (a snapshot is of a resolved round
+  // edge), and as many undrained records as the drain section says it holds
+  const uint64_t n_drain = tab[P0 + POOL_DRAIN].bytes / sizeof(sgn_drain_rec);
+  const auto pools = pool_buffers(S, Z, 0, n_drain);
   auto name_of = [&](size_t i) -> std::string {
-    return i == SEC_CTRL ? "ctrl" : i < P0 ? kStateBufferNames[i - SEC_FIXED] : kPoolNames[i - P0];
+    return i == SEC_CTRL ? "ctrl" : i < P0 ? fixed[i - SEC_FIXED].name : i < T0 ? pools[i - P0].name : kTailNames[i - T0];
   };
   uint64_t total = sizeof(FileHeader) + n_sec * sizeof(TableEnt) + 8;
   for (size_t i = 0; i < n_sec; i++) {
@@ -548,22 +533,16 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
   auto bad_size = [&](size_t i) { return efile("section " + name_of(i) + " has a size this simulation's layout does not give"); };
   if (!size_is(SEC_CTRL, sizeof(Ctrl))) return bad_size(SEC_CTRL);
   for (size_t k = 0; k < fixed.size(); k++)
-    if (!size_is(SEC_FIXED + k, fixed[k].second)) return bad_size(SEC_FIXED + k);
-  if (!size_is(P0 + SECP_CODEL, h.cq_pages * CQ_PAGE * sizeof(CodelEnt))) return bad_size(P0 + SECP_CODEL);
-  if (!size_is(P0 + SECP_CQ_NEXT, h.cq_pages * 4)) return bad_size(P0 + SECP_CQ_NEXT);
-  if (!size_is(P0 + SECP_CQ_FREE, h.cq_pages * 4)) return bad_size(P0 + SECP_CQ_FREE);
-  // (a snapshot is of a resolved round edge: nothing in the spill area)
-  if (!size_is(P0 + SECP_SPILL, 0)) return bad_size(P0 + SECP_SPILL);
-  if (!size_is(P0 + SECP_SPILL_IDX, 0)) return bad_size(P0 + SECP_SPILL_IDX);
-  if (tab[P0 + SECP_DRAIN].bytes % sizeof(sgn_drain_rec) || tab[P0 + SECP_DRAIN].bytes / sizeof(sgn_drain_rec) > S.drain_cap)
-    return bad_size(P0 + SECP_DRAIN);
-  if (tab[P0 + SECP_PACKED].bytes % 32 || !size_is(P0 + SECP_PACKED, h.calendar_runs * sizeof(EvRec))) return bad_size(P0 + SECP_PACKED);
-  if (tab[P0 + SECP_HANDLES].bytes % 8 || tab[P0 + SECP_HANDLES].bytes / 8 > SGN_TAG_SLOT_MASK + 1ull) return bad_size(P0 + SECP_HANDLES);
-  if (!size_is(P0 + SECP_SUBMIT_SEQ, nH * 4)) return bad_size(P0 + SECP_SUBMIT_SEQ);
-  if (tab[P0 + SECP_DRAIN_HELD].bytes % sizeof(sgn_drain_rec)) return bad_size(P0 + SECP_DRAIN_HELD);
-  if (!size_is(P0 + SECP_H_EXT, 0) && !size_is(P0 + SECP_H_EXT, n_slabs * 8)) return bad_size(P0 + SECP_H_EXT);
-  if (!size_is(P0 + SECP_TRACE, h.trace_records * sizeof(sgn_trace_rec))) return bad_size(P0 + SECP_TRACE);
-  if (size_is(P0 + SECP_H_EXT, 0) && h.ext_total) return efile("slab extensions without their table");
+    if (!size_is(SEC_FIXED + k, fixed[k].bytes)) return bad_size(SEC_FIXED + k);
+  for (size_t k = 0; k < POOL_N; k++)  // (drain: whole records, no more than this context's buffer holds)
+    if (!size_is(P0 + k, pools[k].bytes) || (k == POOL_DRAIN && n_drain > S.drain_cap)) return bad_size(P0 + k);
+  if (tab[T0 + SECT_PACKED].bytes % 32 || !size_is(T0 + SECT_PACKED, h.calendar_runs * sizeof(EvRec))) return bad_size(T0 + SECT_PACKED);
+  if (tab[T0 + SECT_HANDLES].bytes % 8 || tab[T0 + SECT_HANDLES].bytes / 8 > SGN_TAG_SLOT_MASK + 1ull) return bad_size(T0 + SECT_HANDLES);
+  if (!size_is(T0 + SECT_SUBMIT_SEQ, nH * 4)) return bad_size(T0 + SECT_SUBMIT_SEQ);
+  if (tab[T0 + SECT_DRAIN_HELD].bytes % sizeof(sgn_drain_rec)) return bad_size(T0 + SECT_DRAIN_HELD);
+  if (!size_is(T0 + SECT_H_EXT, 0) && !size_is(T0 + SECT_H_EXT, n_slabs * 8)) return bad_size(T0 + SECT_H_EXT);
+  if (!size_is(T0 + SECT_TRACE, h.trace_records * sizeof(sgn_trace_rec))) return bad_size(T0 + SECT_TRACE);
+  if (size_is(T0 + SECT_H_EXT, 0) && Z.ext_total) return efile("slab extensions without their table");
 
   // ---- the snapshot's buffers, then the payloads into them
   sgn_snapshot* s = new sgn_snapshot();
@@ -574,24 +553,24 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
     snap_release(s);
     return set_error(ctx, code, m);
   };
+  s->lay = Z;  // (bounded above; restore reads it)
   s->fixed.resize(fixed.size());
-  Buf* pools[] = {&s->codel, &s->cq_next, &s->cq_free, &s->spill, &s->spill_idx, &s->drain, &s->packed};
   bool ok = true;
   for (size_t k = 0; ok && k < fixed.size(); k++) ok = snap_buf_alloc(&s->fixed[k], tab[SEC_FIXED + k].bytes);
-  for (uint32_t k = 0; ok && k <= SECP_PACKED; k++) ok = snap_buf_alloc(pools[k], tab[P0 + k].bytes);
-  ok = ok && snap_buf_alloc(&s->trace, tab[P0 + SECP_TRACE].bytes);
+  for (size_t k = 0; ok && k < POOL_N; k++) ok = snap_buf_alloc(&s->pool[k], tab[P0 + k].bytes);
+  ok = ok && snap_buf_alloc(&s->packed, tab[T0 + SECT_PACKED].bytes) && snap_buf_alloc(&s->trace, tab[T0 + SECT_TRACE].bytes);
   if (!ok) return fail(SGN_ENOMEM, "device allocation failed (snapshot import)");
   try {
-    s->handles.resize(tab[P0 + SECP_HANDLES].bytes / 8);
-    s->submit_seq.resize(tab[P0 + SECP_SUBMIT_SEQ].bytes / 4);
-    s->drain_held.resize(tab[P0 + SECP_DRAIN_HELD].bytes / sizeof(sgn_drain_rec));
-    s->h_ext.resize(tab[P0 + SECP_H_EXT].bytes / 8);
+    s->handles.resize(tab[T0 + SECT_HANDLES].bytes / 8);
+    s->submit_seq.resize(tab[T0 + SECT_SUBMIT_SEQ].bytes / 4);
+    s->drain_held.resize(tab[T0 + SECT_DRAIN_HELD].bytes / sizeof(sgn_drain_rec));
+    s->h_ext.resize(tab[T0 + SECT_H_EXT].bytes / 8);
   } catch (const std::bad_alloc&) {
     return fail(SGN_ENOMEM, "host allocation failed (snapshot import)");
   }
-  Events E;
+  report::ReportEvents<2> E;  // one per staging chunk
   if (!E.make()) return fail(SGN_EDEVICE, "hipEventCreate failed (snapshot import)");
-  std::vector<Sec> secs = sections_of(s, s->trace.d, h.trace_records);  // (the same list export walks)
+  std::vector<Sec> secs = sections_of(S, s, s->trace.d, h.trace_records);  // (the same list export walks)
   const Clock::time_point t_stream = Clock::now();
   bool used[2] = {false, false};
   char padbuf[16];
@@ -643,7 +622,7 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
   if (c.rounds != h.rounds || c.ws != h.ws || c.we != h.we) return fail(SGN_EFILE, w + "the control block is of another round edge than the header");
   if (c.spill_n || c.hold) return fail(SGN_EFILE, w + "the control block is not of a resolved round edge");
   if (c.keep_slab > S.NB) return fail(SGN_EFILE, w + "the control block's spare slab is outside the calendar");
-  if (s->drain.bytes != (S.drain ? std::min<uint64_t>(c.drain_n, S.drain_cap) : 0) * sizeof(sgn_drain_rec))
+  if (n_drain != (S.drain ? std::min<uint64_t>(c.drain_n, S.drain_cap) : 0))
     return fail(SGN_EFILE, w + "section drain does not hold the control block's record count");
   // (the section holds the records [reserved, trace_n) that sgn_trace_take had not handed out)
   if (h.reserved > c.trace_n || h.trace_records > c.trace_n - h.reserved || (!h.traced && h.reserved))
@@ -653,9 +632,9 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
     for (uint64_t e : s->h_ext) {
       if (!e) continue;
       n_ext++;
-      if ((e & EXT_OFF_MASK) + (e >> 40) > h.ext_total) return fail(SGN_EFILE, w + "a slab extension lies outside the extension pool");
+      if ((e & EXT_OFF_MASK) + (e >> 40) > Z.ext_total) return fail(SGN_EFILE, w + "a slab extension lies outside the extension pool");
     }
-    if (n_ext != h.ext_slabs) return fail(SGN_EFILE, w + "the extension table disagrees with the header's count");
+    if (n_ext != h.counters.ext_slabs) return fail(SGN_EFILE, w + "the extension table disagrees with the header's count");
   }
   {  // the scan k_snap_copy<unpack> trusts: the imported fills must add up to the packed runs
     if (!s->h_ext.empty()) {
@@ -664,7 +643,8 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
         return fail(SGN_EDEVICE, w + "a device copy failed");
     }
     uint64_t scan_total = 0;
-    if (int rc = snap_scan_total(ctx, (const uint32_t*)s->fixed[kStateSlabN].d, d_ext, (uint32_t)h.cap, n_slabs, &scan_total))
+    const uint32_t* fills = (const uint32_t*)snap_fixed(s, S, (const void*)S.slab_n)->d;
+    if (int rc = snap_scan_total(ctx, fills, d_ext, (uint32_t)Z.cap, n_slabs, &scan_total))
       return fail(rc, ctx->err);
     if (scan_total != h.calendar_runs)
       return fail(SGN_EFILE, w + "the slab fills add up to " + std::to_string(scan_total) + " runs, the packed calendar holds " +
@@ -676,23 +656,10 @@ int import_one(sgn_ctx* ctx, sgn_read_fn rd, void* user, sgn_snapshot** out) {
   // ---- a snapshot of this context, as sgn_snapshot_save would have left it
   s->ctx = ctx;
   s->gen = ctx->sim_gen;
-  s->S = S;  // (restore reads the five layout scalars below; the pointers are never followed)
-  s->S.CAP = (uint32_t)h.cap;
-  s->S.cq_pages = (uint32_t)h.cq_pages;
-  s->S.spill_cap = h.spill_cap;
-  s->S.ext_total = h.ext_total;
-  s->S.gspec = (uint32_t)h.gspec;
   s->runs = h.calendar_runs;
   s->imported = true;
   s->trace_b = h.reserved;
-  s->rounds_enqueued = h.rounds_enqueued;
-  s->codel_grows = h.codel_grows;
-  s->cal_grows = h.cal_grows;
-  s->cal_spill_runs = h.cal_spill_runs;
-  s->ext_slabs = h.ext_slabs;
-  s->spill_grows = h.spill_grows;
-  s->rounds_held = h.rounds_held;
-  s->codel_allocs_before = h.codel_allocs_before;
+  s->counters = h.counters;
   snap_fill_info(s, n_slabs);
   s->info.save_ms = s->info.pack_ms = 0;
   ctx->snapshots.push_back(s);

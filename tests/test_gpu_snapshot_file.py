@@ -133,7 +133,7 @@ def test_round_trip_periodic(ctxf, oracle, monkeypatch, tmp_path, persistent, tr
 @pytest.mark.parametrize("kind", ["codel", "hot"])
 def test_round_trip_grown_pools(ctxf, oracle, monkeypatch, tmp_path, kind):  # noqa: F811
     keys = ("codel_pages", "slab_capacity", "slab_extensions", "slab_extension_runs", "codel_pool_grows",
-            "calendar_grows", "codel_page_allocs", "rounds_held")
+            "calendar_grows", "codel_page_allocs", "rounds_held", "calendar_spill_runs", "spill_area_grows")
     if kind == "codel":
         args = _codel_args(n=300)
         saved_when = lambda i, s: i["codel_pool_grows"] >= 1  # noqa: E731
