@@ -769,6 +769,45 @@ int sgn_drain_enable(sgn_ctx* ctx, uint64_t capacity);
 int sgn_drain(sgn_ctx* ctx, uint32_t host_lo, uint32_t host_hi, sgn_drain_rec* out, uint64_t cap,
               uint64_t* n_out);
 
+/* ---- additions to ABI 10 (new calls only; no struct of ABI 10 changes): the ordered drain —
+ * every pending record in one call, ordered on the device, with per-host spans, all or nothing
+ * (the form of sgn_trace_take; sgn_drain above stays the range form). DESIGN.md §7f. ---- */
+
+/* Drain records produced and not yet returned: those on the device plus those an earlier
+ * sgn_drain left held on the host (another host range, a short cap). */
+int sgn_drain_pending(sgn_ctx* ctx, uint64_t* n);
+
+/* Between rounds: moves EVERY pending record out, ordered on the device by sgn_drain's key
+ * (host, time, src_host, src_eid, tag, status), with one span per host that has records
+ * (ascending HostId; sgn_trace_span: out[first .. first + count)). The result is byte for byte
+ * what sgn_drain(ctx, 0, 0xFFFFFFFF, out, enough, &n) would return at that point, handle included
+ * (the shard rule above), and the context is left as that call would leave it: nothing on the
+ * device, nothing held. Records an earlier sgn_drain left held are part of the take.
+ * All or nothing: with cap below the pending count, or spans != NULL and span_cap below the
+ * hosts with records, SGN_ERANGE, *n_out and *n_spans say what is needed, and nothing is taken or
+ * changed; the same call with larger arrays then succeeds. spans may be NULL with span_cap 0.
+ * With nothing pending: SGN_OK, both counts 0, nothing is launched.
+ * The simulation does not change (window, counters, digests, traces, sampler and backlog are
+ * those of a run with sgn_drain in its place); snapshots save and restore pending records as
+ * they do for sgn_drain. Works on any context and is not a collective: a shard takes the records
+ * of the hosts it owns. A record whose host lies outside the owned range is SGN_EDEVICE (the
+ * message names the host) with nothing taken.
+ * Errors: SGN_EINVAL for a null ctx or n_out, or a null array with a non-zero capacity;
+ * SGN_ESTATE without a simulation or with traffic other than EXTERNAL; SGN_ENOMEM with nothing
+ * changed; SGN_EDEVICE for a HIP failure. */
+int sgn_drain_take(sgn_ctx* ctx, sgn_drain_rec* out, uint64_t cap, uint64_t* n_out,
+                   sgn_trace_span* spans, uint64_t span_cap, uint64_t* n_spans);
+
+/* What the context's last sgn_drain_take (or sgn_selftest_drain_order) spent (measurements;
+ * tools/drain_timing.py). wave_max and tile are always filled. */
+typedef struct sgn_drain_take_timing {
+  double total_ms, kernel_ms[4] /* count, scan, scatter, order */, copy_ms;
+  uint64_t records, hosts, largest_span;
+  uint64_t spans_by_class[3];   /* ordered by a wave / by one workgroup in LDS / by tiles + merge */
+  uint32_t wave_max, tile;      /* the class limits: records a wave, and a workgroup, orders at once */
+} sgn_drain_take_timing;
+int sgn_drain_take_timing_get(sgn_ctx* ctx, sgn_drain_take_timing* out);
+
 /* The next window, decided by a caller that also runs hosts of its own (Controller with CPU
  * hosts, controller.rs:88-112): [start, end) with previous window end <= start <= the
  * device's minimum next event time (sgn_window's start), start < end, end - start <= the
@@ -986,6 +1025,16 @@ int sgn_selftest_codel_law(sgn_ctx* ctx, uint64_t n, uint64_t* out);
  * tiles of 1024) on the caller's n counts: off_out[j] = counts[0] + ... + counts[j - 1], *total_out
  * their sum. Needs no simulation; for checking the carry from tile to tile. */
 int sgn_selftest_report_scan(sgn_ctx* ctx, const uint32_t* counts, uint32_t n, uint32_t* off_out, uint64_t* total_out);
+
+/* sgn_drain_take's kernels (count, scan, scatter, order) on the caller's n records of hosts
+ * [host_lo, host_lo + n_hosts): out gets them ordered by (host, time, src_host, src_eid, tag,
+ * status), spans (may be NULL with span_cap 0) one entry per host with records; span_cap below
+ * that count is SGN_ERANGE with *n_spans the count. Needs no simulation; handle is copied through
+ * untouched. Records with equal keys come out in an unspecified order. A record of a host outside
+ * the range is SGN_EDEVICE with out untouched. */
+int sgn_selftest_drain_order(sgn_ctx* ctx, const sgn_drain_rec* recs, uint64_t n, uint32_t host_lo,
+                             uint32_t n_hosts, sgn_drain_rec* out, sgn_trace_span* spans,
+                             uint64_t span_cap, uint64_t* n_spans);
 
 /* The section digest of snapshot files, for len % 4 == 0: with w_j the little-endian u64 at byte
  * 8j (a 4-byte tail zero-extended), D = mix64(len ^ SGN_DIGEST_SEED) + sum_j mix64(w_j ^

@@ -863,6 +863,13 @@ struct sgn_ctx {
   sgn::report::ReportEvents<8> bk_ev;
   bool bk_timed = false;                  // bk_timing is of a sgn_backlog of this simulation
   sgn_backlog_timing bk_timing{};
+  // the ordered drain (drain_take.hip): its device scratch (header, per-host words, spans, two record
+  // buffers, the uploaded held records), grown when a take needs more, and the HIP events of the
+  // timing. Allocated by the first take, dropped by sgn_sim_init (drain_take_release).
+  void* dt_mem = nullptr;
+  size_t dt_bytes = 0;
+  sgn::report::ReportEvents<8> dt_ev;
+  sgn_drain_take_timing dt_timing{};      // of the last sgn_drain_take or sgn_selftest_drain_order
   uint64_t drain_cap = 0;                 // sgn_drain_enable (EXTERNAL traffic)
   std::vector<uint64_t> handles;          // sgn_submit handles by slot (tag & ~SGN_TAG_EXT)
   std::vector<uint32_t> submit_seq;       // per owned host: submissions so far
@@ -1061,6 +1068,8 @@ int trace_view_set(sgn_ctx* ctx, uint64_t base);
 void sample_release(sgn_ctx* ctx);
 // ---- backlog.hip: the backlog report's scratch, staging buffer and events (free_sim) ----
 void backlog_release(sgn_ctx* ctx);
+// ---- drain_take.hip: the ordered drain's scratch and events (free_sim) ----
+void drain_take_release(sgn_ctx* ctx);
 // records of the context's trace buffer that a reader may copy now: [trace_base, min(n, trace_base
 // + trace_cap)) for a control block that counts n (n below the cursor: none)
 inline uint64_t trace_held(const sgn_ctx* ctx, uint64_t n) {
@@ -1091,6 +1100,7 @@ uint64_t layout_sig_snapshot_file();
 uint64_t layout_sig_trace_take();
 uint64_t layout_sig_sample();
 uint64_t layout_sig_backlog();
+uint64_t layout_sig_drain_take();
 }  // namespace sgn
 
 #define SGN_HIP(ctx, call)                                   \

@@ -152,6 +152,7 @@ void free_sim(sgn_ctx* ctx) {
   ctx->take_bytes = 0;
   sample_release(ctx);
   backlog_release(ctx);
+  drain_take_release(ctx);
   ctx->trace_buf = nullptr;  // (in allocs)
   ctx->trace_base = 0;
   ctx->trace_held = 0;

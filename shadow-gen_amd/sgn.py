@@ -215,6 +215,12 @@ DRAIN_DTYPE = np.dtype([("time", "<u8"), ("src_eid", "<u8"), ("handle", "<u8"), 
 assert DRAIN_DTYPE.itemsize == C.sizeof(DrainRec)
 
 
+class DrainTakeTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_double), ("kernel_ms", C.c_double * 4), ("copy_ms", C.c_double),
+                ("records", C.c_uint64), ("hosts", C.c_uint64), ("largest_span", C.c_uint64),
+                ("spans_by_class", C.c_uint64 * 3), ("wave_max", C.c_uint32), ("tile", C.c_uint32)]
+
+
 def pkt_soa(src_host, dst_ip, payload_len, send_time, handle=None, wire_len=None):
     """(PktSoa, keep-alive arrays) for sgn_submit / ora_sim_submit."""
     a = [np.ascontiguousarray(src_host, dtype=np.uint32), np.ascontiguousarray(dst_ip, dtype=np.uint32),
@@ -368,6 +374,11 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         "sgn_submit": (C.c_int, [vp, C.POINTER(PktSoa)]),
         "sgn_drain_enable": (C.c_int, [vp, C.c_uint64]),
         "sgn_drain": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.POINTER(DrainRec), C.c_uint64, u64p]),
+        "sgn_drain_pending": (C.c_int, [vp, u64p]),
+        "sgn_drain_take": (C.c_int, [vp, C.POINTER(DrainRec), C.c_uint64, u64p, C.POINTER(TraceSpan), C.c_uint64, u64p]),
+        "sgn_drain_take_timing_get": (C.c_int, [vp, C.POINTER(DrainTakeTiming)]),
+        "sgn_selftest_drain_order": (C.c_int, [vp, C.POINTER(DrainRec), C.c_uint64, C.c_uint32, C.c_uint32,
+                                               C.POINTER(DrainRec), C.POINTER(TraceSpan), C.c_uint64, u64p]),
         "sgn_set_window": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
         "sgn_rng_next_u64": (C.c_int, [vp, C.c_uint32, u64p]),
         "sgn_rng_double": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_double)]),
@@ -814,6 +825,45 @@ class Context:
         self.check(self.L.sgn_drain(self.h, lo, hi, out.ctypes.data_as(C.POINTER(DrainRec)), cap, C.byref(n)))
         return out[: n.value]
 
+    def drain_pending(self):
+        """Drain records produced and not yet returned (on the device, or held by an earlier drain)."""
+        n = C.c_uint64()
+        self.check(self.L.sgn_drain_pending(self.h, C.byref(n)))
+        return n.value
+
+    def drain_take(self, cap=None, span_cap=None):
+        """(records, spans): EVERY pending drain record, ordered on the device by drain()'s key, and
+        one span {host, first, count} per host with records (ascending host). Nothing is pending
+        afterwards. By default the arrays are sized from drain_pending() and the call is repeated
+        once with the counts an ERANGE carries; with cap / span_cap given, too small raises
+        SgnError with rc ERANGE, .needed = (records, spans), and takes nothing."""
+        sized = cap is None and span_cap is None
+        if cap is None:
+            cap = self.drain_pending()
+        if span_cap is None:
+            span_cap = min(cap, self._hosts.n)
+        for attempt in (0, 1):
+            recs = np.zeros(cap, dtype=DRAIN_DTYPE)
+            spans = np.zeros(span_cap, dtype=SPAN_DTYPE)
+            n, ns = C.c_uint64(), C.c_uint64()
+            rc = self.L.sgn_drain_take(self.h, recs.ctypes.data_as(C.POINTER(DrainRec)) if cap else None, cap, C.byref(n),
+                                       spans.ctypes.data_as(C.POINTER(TraceSpan)) if span_cap else None, span_cap, C.byref(ns))
+            if rc == ERANGE and sized and attempt == 0:
+                cap, span_cap = n.value, ns.value
+                continue
+            if rc != 0:
+                e = SgnError(rc, self.L.sgn_last_error(self.h).decode())
+                e.needed = (n.value, ns.value)
+                raise e
+            return recs[: n.value], spans[: ns.value]
+
+    def drain_take_timing(self):
+        t = DrainTakeTiming()
+        self.check(self.L.sgn_drain_take_timing_get(self.h, C.byref(t)))
+        return {"total_ms": t.total_ms, "kernel_ms": list(t.kernel_ms), "copy_ms": t.copy_ms, "records": t.records,
+                "hosts": t.hosts, "largest_span": t.largest_span, "spans_by_class": list(t.spans_by_class),
+                "wave_max": t.wave_max, "tile": t.tile}
+
     def set_window(self, start, end):
         self.check(self.L.sgn_set_window(self.h, start, end))
 
@@ -902,6 +952,26 @@ def _shards_call(shards, name, *args):
         after = errs()
         new = [a for a, b in zip(after, before) if a != b] or [a for a in after if a]
         raise SgnError(rc, new[0] if new else name + ": invalid argument")
+
+
+def selftest_drain_order(ctx, recs, host_lo, n_hosts, span_cap=None):
+    """drain_take's kernels on the caller's records (DRAIN_DTYPE) of hosts [host_lo, host_lo +
+    n_hosts): (ordered records, spans). Needs no simulation; handle is copied through. An error
+    (SgnError) carries the output array as .out and the span count as .needed."""
+    recs = np.ascontiguousarray(recs, dtype=DRAIN_DTYPE)
+    n = len(recs)
+    span_cap = min(n, n_hosts) if span_cap is None else span_cap
+    out = np.zeros(n, dtype=DRAIN_DTYPE)
+    spans = np.zeros(span_cap, dtype=SPAN_DTYPE)
+    ns = C.c_uint64()
+    rc = ctx.L.sgn_selftest_drain_order(ctx.h, recs.ctypes.data_as(C.POINTER(DrainRec)) if n else None, n, host_lo, n_hosts,
+                                        out.ctypes.data_as(C.POINTER(DrainRec)) if n else None,
+                                        spans.ctypes.data_as(C.POINTER(TraceSpan)) if span_cap else None, span_cap, C.byref(ns))
+    if rc != 0:
+        e = SgnError(rc, ctx.L.sgn_last_error(ctx.h).decode())
+        e.out, e.needed = out, ns.value
+        raise e
+    return out, spans[: ns.value]
 
 
 def shards_run_until(shards, t_emulated):
