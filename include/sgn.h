@@ -808,6 +808,94 @@ typedef struct sgn_drain_take_timing {
 } sgn_drain_take_timing;
 int sgn_drain_take_timing_get(sgn_ctx* ctx, sgn_drain_take_timing* out);
 
+/* ---- additions to ABI 10 (new calls only; no struct of ABI 10 changes): the router delay report —
+ * how long every packet spent at its destination's router (the CoDel queue, then the wait for the
+ * downlink token bucket) before it was handed to the interface or dropped, folded on the device
+ * from the trace. The ROUTER DELAY of a packet at host h is the `a` of its exit record
+ * (SGN_TRACE_DELIVER or SGN_TRACE_CODEL_DROP) minus the `a` of its SGN_TRACE_POP record; loopback
+ * (SGN_TRACE_LOCAL) packets never enter the router and are not counted. Within one host the router
+ * is FIFO, so the k-th exit of a host pairs with its k-th POP: the report ranks the pops and the
+ * exits inside the per-host spans a take already builds and matches them there; no record leaves
+ * the device. Packets in the router when an interval ends carry over to the next fold (the CARRY:
+ * per owned host the FIFO of packets popped and not yet exited — pop time, source host, source
+ * event id — in device memory, grown on demand). DESIGN.md §7g.
+ * Histogram bins: bin 0 holds delay == 0, bin k (1 <= k <= 46) holds 2^(k-1) <= delay < 2^k ns,
+ * bin 47 everything from 2^46 ns up. ---- */
+
+#define SGN_DELAY_BINS 48
+typedef struct sgn_delay_row {      /* 64 B: one per owned host with anything to report */
+  uint32_t host, reserved;
+  uint32_t standing;                /* carry length now: packets popped into the router and not yet exited */
+  uint32_t unmatched;               /* exits that met an unknown entry (a packet that stood there at sgn_delay_enable) */
+  uint64_t delivered, dropped;      /* matched exits by kind (DELIVER / CODEL_DROP) */
+  uint64_t delay_sum_delivered, delay_sum_dropped;   /* ns */
+  uint64_t delay_max;               /* over both kinds */
+  uint64_t standing_oldest;         /* pop time of the carry's head; SGN_EMUTIME_INVALID when empty or unknown */
+} sgn_delay_row;
+typedef struct sgn_delay_info {
+  uint64_t rounds, window_start, window_end;   /* the round edge of the last fold (sgn_window) */
+  uint64_t folds, records;                     /* folds, and trace records folded, since enable / clear */
+  uint64_t hosts, rows;                        /* owned hosts; hosts with a row */
+  uint64_t total[6];   /* delivered, dropped, delay_sum_delivered, delay_sum_dropped, standing, unmatched */
+  uint64_t delay_max;  uint32_t delay_max_host, pad0;   /* over the hosts with a matched exit: lowest HostId on
+                                                           equal values; 0 / 0 when none */
+  uint64_t hist_delivered[SGN_DELAY_BINS], hist_dropped[SGN_DELAY_BINS];
+} sgn_delay_info;
+
+/* After sgn_sim_init on a context with a trace, between calls. SGN_ESTATE without a simulation,
+ * without a trace, or with trace records pending (sgn_trace_take them first: the record stream and
+ * the device state then meet at one round edge). Zeroes the accumulators and seeds each owned
+ * host's carry with as many UNKNOWN entries (pop time SGN_EMUTIME_INVALID) as packets stand at its
+ * router now: the CoDel queue's length plus the packet relay_inet_in holds (sgn_backlog's
+ * router_packets and SGN_BACKLOG_ROUTER_HELD, by the same reader). Right after sgn_sim_init that
+ * is nothing. An exit that meets an unknown entry counts as `unmatched` and enters no statistic.
+ * May be called again at any time (the report starts over from the state as it is now).
+ * SGN_ENOMEM leaves the context without the report. */
+int sgn_delay_enable(sgn_ctx* ctx);
+
+/* Between calls: a take whose records stay on the device. Orders every pending trace record as
+ * sgn_trace_take does (the same kernels and checks), folds them into the report and empties the
+ * trace buffer. With nothing pending: SGN_OK, only `folds` advances. All or nothing: on any error
+ * nothing is consumed, accumulators and carry are unchanged. SGN_EDEVICE, naming the first host,
+ * when a host has more exits than carry plus pops, when an exit comes before its pop, or when a
+ * matched pair disagrees in (peer, c) or has its exit time before its pop time. out (may be NULL)
+ * gets the info sgn_delay_get would return.
+ * On a context with the report enabled sgn_trace_take folds the same ordered records before it
+ * copies them out; its output bytes, spans and counts are what they are without the report, so
+ * captures and the report work together (the two calls share one function).
+ * Rewinds: the report remembers the trace position it has folded up to. When a fold or take finds
+ * the context's taken count different from it (sgn_snapshot_restore moved it back), SGN_ESTATE and
+ * nothing changes, until sgn_delay_enable is called again. The report is not part of a snapshot
+ * or a snapshot file.
+ * Works on any context for the hosts it owns and is not a collective (pop and exit both happen at
+ * the destination). With sgn_trace_hosts only the listed hosts produce records and rows. */
+int sgn_delay_fold(sgn_ctx* ctx, sgn_delay_info* out /* may be NULL */);
+
+/* Rows for every owned host with a non-zero standing, unmatched, delivered or dropped, ascending
+ * by HostId, compacted on the device (count, scan, scatter); totals, maxima and both histograms
+ * are folded on the device. out == NULL with cap == 0 asks for the totals only; with out != NULL
+ * and cap below the row count SGN_ERANGE, *n_out says what is needed, info is filled and nothing
+ * is written to out (sgn_backlog's rules). Read-only, cumulative since the last enable or clear.
+ * Errors: null ctx, n_out or info SGN_EINVAL; report not enabled SGN_ESTATE. */
+int sgn_delay_get(sgn_ctx* ctx, sgn_delay_row* out, uint64_t cap, uint64_t* n_out, sgn_delay_info* info);
+
+/* Zeroes the accumulators, both histograms, folds and records. The carry stays, so a caller makes
+ * intervals with get + clear and loses no match. */
+int sgn_delay_clear(sgn_ctx* ctx);
+
+/* What the context's last fold spent (sgn_delay_fold, sgn_trace_take with the report enabled, or
+ * sgn_selftest_delay_fold's last piece; tools/delay_timing.py). wave_max and tile are always
+ * filled. */
+typedef struct sgn_delay_timing {
+  double total_ms;       /* wall time of the call */
+  double order_ms[3];    /* the take's kernels: count, scan, scatter */
+  double kernel_ms[5];   /* per-host pop / exit counts; carry scan; carry survivors; rank and match; commit */
+  uint64_t records, hosts, largest_span, carry_entries;
+  uint64_t spans_by_class[2];   /* matched by a wave / walked by a workgroup */
+  uint32_t wave_max, tile;      /* the class limits: records a wave, and a workgroup per pass, handle at once */
+} sgn_delay_timing;
+int sgn_delay_timing_get(sgn_ctx* ctx, sgn_delay_timing* out);
+
 /* The next window, decided by a caller that also runs hosts of its own (Controller with CPU
  * hosts, controller.rs:88-112): [start, end) with previous window end <= start <= the
  * device's minimum next event time (sgn_window's start), start < end, end - start <= the
@@ -1035,6 +1123,17 @@ int sgn_selftest_report_scan(sgn_ctx* ctx, const uint32_t* counts, uint32_t n, u
 int sgn_selftest_drain_order(sgn_ctx* ctx, const sgn_drain_rec* recs, uint64_t n, uint32_t host_lo,
                              uint32_t n_hosts, sgn_drain_rec* out, sgn_trace_span* spans,
                              uint64_t span_cap, uint64_t* n_spans);
+
+/* The router delay report's kernels (the take's ordering, then count, scan, carry, rank and match,
+ * commit, and sgn_delay_get's compaction) without a simulation: the caller's records of hosts
+ * [host_lo, host_lo + n_hosts), in any order, are n_pieces consecutive intervals, piece i being
+ * recs[piece_ends[i - 1] .. piece_ends[i]) (piece_ends ascending; every host's records of a piece
+ * carry consecutive seq). The carry starts from standing0[h] unknown entries per host (NULL: none).
+ * rows / cap / n_rows / info as sgn_delay_get after the last piece. An enabled report of the
+ * context is left alone. */
+int sgn_selftest_delay_fold(sgn_ctx* ctx, const sgn_trace_rec* recs, const uint64_t* piece_ends, uint32_t n_pieces,
+                            uint32_t host_lo, uint32_t n_hosts, const uint32_t* standing0 /* may be NULL */,
+                            sgn_delay_row* rows, uint64_t cap, uint64_t* n_rows, sgn_delay_info* info);
 
 /* The section digest of snapshot files, for len % 4 == 0: with w_j the little-endian u64 at byte
  * 8j (a 4-byte tail zero-extended), D = mix64(len ^ SGN_DIGEST_SEED) + sum_j mix64(w_j ^

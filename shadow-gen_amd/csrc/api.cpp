@@ -140,7 +140,8 @@ int sgn_create(sgn_ctx** out, const sgn_create_opts* opts) {
       sgn::layout_sig_run() != kLayoutSig || sgn::layout_sig_pools() != kLayoutSig ||
       sgn::layout_sig_interop() != kLayoutSig || sgn::layout_sig_snapshot_file() != kLayoutSig ||
       sgn::layout_sig_trace_take() != kLayoutSig || sgn::layout_sig_sample() != kLayoutSig ||
-      sgn::layout_sig_backlog() != kLayoutSig || sgn::layout_sig_drain_take() != kLayoutSig) {
+      sgn::layout_sig_backlog() != kLayoutSig || sgn::layout_sig_drain_take() != kLayoutSig ||
+      sgn::layout_sig_delay() != kLayoutSig) {
     g_create_error = "libsgn's objects were compiled against different versions of sgn_internal.h (rebuild all of them)";
     return SGN_ESTATE;
   }

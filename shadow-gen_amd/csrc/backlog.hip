@@ -31,11 +31,13 @@
 #include <cstring>
 #include <string>
 
+#include "backlog_read.h"
 #include "report_common.h"
 #include "sgn_workload.h"
 
 using namespace sgn;
 using namespace sgn::report;  // the scan (kScanTile = 1024 waves a tile), the wave reductions, the host scaffolding
+using namespace sgn::backlog_read;  // BkArgs, BkHost, bk_load, bk_args: shared with delay.hip
 
 // ---- device side ----------------------------------------------------------------------------
 namespace {
@@ -79,23 +81,6 @@ struct __attribute__((aligned(16))) BkCal {
   uint64_t pad;
 };
 static_assert(sizeof(BkCal) == 32, "");
-
-// what the kernels read of the simulation (plain pointers; the sizes that bound every index)
-struct BkArgs {
-  const HostRec* hrec;        // [nH] by slot
-  const uint64_t* htile;      // PERIODIC: the hot lines, tiled (hot_idx), else null
-  const uint32_t* sid_of;     // [n_all] HostId -> lo + slot
-  const uint32_t* host_of;    // [nH] slot -> HostId
-  const CodelEnt* codel;      // [cq_pages * CQ_PAGE]
-  const FifoEnt* fifo;        // [nH * fifo_cap]
-  const EvRec* pool;          // [(NB + 1) * G * CAP]
-  const uint32_t* slab_n;     // [(NB + 1) * G]
-  const uint32_t* bucket_slab;  // [NB]
-  const uint64_t* ext;        // [(NB + 1) * G] or null
-  const EvRec* ext_pool;      // [ext_total]
-  uint64_t ext_total;
-  uint32_t lo, nH, n_all, NB, G, CAP, gsh, fifo_cap, cq_pages, tkind;
-};
 
 // 1. the calendar pass. A group's pending runs are in its slab of each of the NB buckets (between
 // rounds the spare slab set is empty): the workgroup's waves take the buckets in turn, a wave's
@@ -168,43 +153,6 @@ __global__ __launch_bounds__(kCalThreads) void k_backlog_calendar(BkArgs a, BkCa
   if (threadIdx.x == 0 && s_runs) atomicAdd((unsigned long long*)&hdr->calendar_runs, (unsigned long long)s_runs);
 }
 
-// the queues' bookkeeping of owned host i (HostId lo + i)
-struct BkHost {
-  uint32_t slot, flags;  // SGN_BACKLOG_*
-  uint32_t cq_len, cq_head, fq_head, fq_len;
-  uint64_t cq_bytes;
-};
-// false: the host's slot is not this shard's. A PERIODIC host with F_COLD clear ended its last
-// round idle: both queues empty, nothing held — its cold lines may hold what an earlier round left
-// there and are not read (HostExec::load's rule).
-__device__ __forceinline__ bool bk_load(const BkArgs& a, uint32_t i, BkHost* h) {
-  const uint32_t slot = a.sid_of[a.lo + i] - a.lo;
-  if (slot >= a.nH) return false;
-  const HostRec* r = a.hrec + slot;
-  uint32_t fl, cq_head;
-  if (a.htile) {  // chunk 7 of the tiled hot line: {app_k, flags | cq_head << 32}
-    const uint64_t w = a.htile[2 * hot_idx(slot, 7) + 1];
-    fl = (uint32_t)w;
-    cq_head = (uint32_t)(w >> 32);
-  } else {
-    fl = r->flags;
-    cq_head = r->cq_head;
-  }
-  h->slot = slot;
-  h->cq_head = cq_head;
-  if (a.tkind == SGN_TRAFFIC_PERIODIC && !(fl & F_COLD)) {
-    h->flags = 0;
-    h->cq_len = h->fq_head = h->fq_len = 0;
-    h->cq_bytes = 0;
-    return true;
-  }
-  h->flags = (fl & F_RI_NEXT ? SGN_BACKLOG_ROUTER_HELD : 0u) | (fl & F_RO_NEXT ? SGN_BACKLOG_OUT_HELD : 0u);
-  h->cq_len = r->cq_len;
-  h->fq_head = r->fq_head;
-  h->fq_len = r->fq_len;
-  h->cq_bytes = r->cq_bytes;
-  return true;
-}
 __device__ __forceinline__ bool bk_has_row(const BkHost& h, const BkCal& c) {
   return (h.flags | h.cq_len | h.fq_len | c.packets | c.submit) != 0 || h.cq_bytes != 0;
 }
@@ -393,34 +341,6 @@ BkLay bk_lay(uint32_t nH) {
   return l;
 }
 size_t bk_stage_bytes(uint32_t nH) { return sizeof(BkHdr) + std::min<uint64_t>(std::max<uint32_t>(nH, 1u), kStageRows) * sizeof(sgn_backlog_row); }
-
-BkArgs bk_args(const sgn_ctx* ctx) {
-  const DevSim& S = ctx->S;
-  BkArgs a;
-  a.hrec = (const HostRec*)S.hrec;
-  a.htile = (const uint64_t*)S.htile;
-  a.sid_of = (const uint32_t*)S.sid_of;
-  a.host_of = (const uint32_t*)S.host_of;
-  a.codel = (const CodelEnt*)S.codel;
-  a.fifo = (const FifoEnt*)S.fifo;
-  a.pool = (const EvRec*)S.pool;
-  a.slab_n = (const uint32_t*)S.slab_n;
-  a.bucket_slab = (const uint32_t*)S.bucket_slab;
-  a.ext = (const uint64_t*)S.ext;
-  a.ext_pool = (const EvRec*)S.ext_pool;
-  a.ext_total = S.ext ? S.ext_total : 0;
-  a.lo = S.lo;
-  a.nH = S.nH;
-  a.n_all = S.n_all;
-  a.NB = S.NB;
-  a.G = S.G;
-  a.CAP = S.CAP;
-  a.gsh = S.gsh;
-  a.fifo_cap = S.fifo_cap;
-  a.cq_pages = S.cq_pages;
-  a.tkind = S.tkind;
-  return a;
-}
 
 int bk_bad(sgn_ctx* ctx, const BkHdr& h) {
   const char* why = h.err & BK_ESLOT    ? "a host's slot lies outside the shard: host "

@@ -774,6 +774,9 @@ struct SimCounters {
 
 }  // namespace sgn
 
+namespace sgn {
+struct DelayState;  // delay.hip
+}
 struct sgn_ctx;
 // A CPU worker thread's staging buffer for sgn_submit (sgn_stage_*).
 struct sgn_stage {
@@ -870,6 +873,11 @@ struct sgn_ctx {
   size_t dt_bytes = 0;
   sgn::report::ReportEvents<8> dt_ev;
   sgn_drain_take_timing dt_timing{};      // of the last sgn_drain_take or sgn_selftest_drain_order
+  // the router delay report (delay.hip): per-host accumulators, both histograms and the double-
+  // buffered carry on the device, with the trace position it has folded up to. Made by
+  // sgn_delay_enable, dropped by sgn_sim_init and sgn_destroy (delay_release); not part of a snapshot.
+  sgn::DelayState* dl = nullptr;
+  sgn_delay_timing dl_timing{};           // of the last fold (a self-test's included)
   uint64_t drain_cap = 0;                 // sgn_drain_enable (EXTERNAL traffic)
   std::vector<uint64_t> handles;          // sgn_submit handles by slot (tag & ~SGN_TAG_EXT)
   std::vector<uint32_t> submit_seq;       // per owned host: submissions so far
@@ -1064,6 +1072,34 @@ int inject_runs(sgn_ctx* ctx, const std::vector<EvRec>& runs);  // into the cale
 // DevSim::trace / trace_cap from trace_buf, trace_cap and the cursor `base`, on the host and on the
 // device (every caller changes the cursor between launches, with the stream idle)
 int trace_view_set(sgn_ctx* ctx, uint64_t base);
+// One take on n device records of hosts [lo, lo + nH) (trace_take.hip): ordered by (host, seq) into
+// the take scratch, folded into dl when it is given, copied to out unless discard. d_src null: the
+// n records at the scratch's upload area (take_upload put them there). Touches nothing of the
+// simulation: sgn_trace_take, sgn_delay_fold and sgn_selftest_delay_fold do that around it.
+int take_run(sgn_ctx* ctx, const char* what, const sgn_trace_rec* d_src, uint64_t n, uint64_t n_up, uint32_t lo, uint32_t nH,
+             bool discard, sgn_trace_rec* out, uint64_t cap, uint64_t* n_out, sgn_trace_span* spans, uint64_t span_cap,
+             uint64_t* n_spans, DelayState* dl);
+int take_upload(sgn_ctx* ctx, const char* what, const sgn_trace_rec* recs, uint64_t n, uint32_t nH);
+// sgn_trace_take and sgn_delay_fold (out null with discard: the records stay on the device)
+int trace_take_common(sgn_ctx* ctx, const char* what, bool discard, sgn_trace_rec* out, uint64_t cap, uint64_t* n_out,
+                      sgn_trace_span* spans, uint64_t span_cap, uint64_t* n_spans);
+// ---- delay.hip: the router delay report ----
+// what a take hands the fold: the ordered records, their spans, the per-host counts and offsets
+struct DelayFoldIn {
+  const uint64_t* staging;
+  const sgn_trace_span* spans;
+  const unsigned long long* cnt;
+  const uint64_t* off;
+  uint64_t n, n_spans;
+  uint32_t lo, nH;
+};
+// prepare runs every kernel up to the error check and changes nothing the report keeps; commit adds
+// the fold's deltas and swaps the carry. position: the trace position folded up to (the context's).
+int delay_fold_prepare(sgn_ctx* ctx, DelayState* st, const DelayFoldIn& in, const char* what);
+int delay_fold_commit(sgn_ctx* ctx, DelayState* st, uint64_t n_records);
+int delay_position_check(sgn_ctx* ctx, const char* what);  // SGN_ESTATE after a rewind or a foreign take
+void delay_position_set(sgn_ctx* ctx, uint64_t pos, bool folded);
+void delay_release(sgn_ctx* ctx);
 // ---- sample.hip: the interval sampler's buffers and events (free_sim: a new simulation has none) ----
 void sample_release(sgn_ctx* ctx);
 // ---- backlog.hip: the backlog report's scratch, staging buffer and events (free_sim) ----
@@ -1101,6 +1137,7 @@ uint64_t layout_sig_trace_take();
 uint64_t layout_sig_sample();
 uint64_t layout_sig_backlog();
 uint64_t layout_sig_drain_take();
+uint64_t layout_sig_delay();
 }  // namespace sgn
 
 #define SGN_HIP(ctx, call)                                   \

@@ -153,6 +153,7 @@ void free_sim(sgn_ctx* ctx) {
   sample_release(ctx);
   backlog_release(ctx);
   drain_take_release(ctx);
+  delay_release(ctx);
   ctx->trace_buf = nullptr;  // (in allocs)
   ctx->trace_base = 0;
   ctx->trace_held = 0;

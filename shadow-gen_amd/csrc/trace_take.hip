@@ -189,11 +189,12 @@ __global__ __launch_bounds__(kTakeThreads) void k_take_scatter(const sgn_trace_r
 // ---- host side ------------------------------------------------------------------------------
 namespace {
 
-// the scratch of one take: header, per-host words, spans, the staging records
+// the scratch of one take: header, per-host words, spans, the staging records, and the upload area
+// of a take whose records come from the host (the delay report's self-test)
 struct TakeLay {
-  size_t hdr, cnt, mx, mn, off, spans, staging, bytes;
+  size_t hdr, cnt, mx, mn, off, spans, staging, up, bytes;
 };
-TakeLay take_lay(uint32_t nH, uint64_t n_spans, uint64_t n) {
+TakeLay take_lay(uint32_t nH, uint64_t n_spans, uint64_t n, uint64_t n_up) {
   ScratchLay s;
   TakeLay l;
   l.hdr = s.take(sizeof(TakeHdr), 16);
@@ -203,12 +204,26 @@ TakeLay take_lay(uint32_t nH, uint64_t n_spans, uint64_t n) {
   l.off = s.take((size_t)nH * 8, 8);
   l.spans = s.take((size_t)n_spans * sizeof(sgn_trace_span), 16);
   l.staging = s.take((size_t)n * sizeof(sgn_trace_rec), 16);
+  l.up = s.take((size_t)n_up * sizeof(sgn_trace_rec), 16);
   l.bytes = s.bytes;
   return l;
 }
 int take_precheck(sgn_ctx* ctx, const char* what) {
   if (!ctx->sim_ready) return set_error(ctx, SGN_ESTATE, "no simulation");
   if (!ctx->trace_buf) return set_error(ctx, SGN_ESTATE, std::string(what) + ": the simulation keeps no trace (sgn_trace_enable)");
+  return 0;
+}
+int take_ensure(sgn_ctx* ctx, const char* what, size_t bytes) {
+  if (ctx->take_bytes >= bytes) return 0;
+  if (ctx->take_mem) (void)hipFree(ctx->take_mem);
+  ctx->take_mem = nullptr;
+  ctx->take_bytes = 0;
+  if (hipMalloc(&ctx->take_mem, bytes) != hipSuccess) {
+    ctx->take_mem = nullptr;
+    (void)hipGetLastError();
+    return set_error(ctx, SGN_ENOMEM, std::string("device allocation failed (") + what + ")");
+  }
+  ctx->take_bytes = bytes;
   return 0;
 }
 
@@ -228,6 +243,128 @@ int trace_view_set(sgn_ctx* ctx, uint64_t base) {
   SGN_HIP(ctx, hipMemcpy((char*)ctx->d_S + offsetof(DevSim, trace), (const char*)&S + offsetof(DevSim, trace), 16,
                          hipMemcpyHostToDevice));
   drop_graph(ctx);  // (a captured batch was made for the DevSim of its time)
+  return 0;
+}
+
+int take_upload(sgn_ctx* ctx, const char* what, const sgn_trace_rec* recs, uint64_t n, uint32_t nH) {
+  const TakeLay L = take_lay(nH, std::min<uint64_t>(nH, n), n, n);
+  if (int rc = take_ensure(ctx, what, L.bytes)) return rc;
+  SGN_HIP(ctx, hipMemcpyAsync((char*)ctx->take_mem + L.up, recs, n * sizeof(sgn_trace_rec), hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+
+int take_run(sgn_ctx* ctx, const char* what, const sgn_trace_rec* d_src, uint64_t n, uint64_t n_up, uint32_t lo, uint32_t nH,
+             bool discard, sgn_trace_rec* out, uint64_t cap, uint64_t* n_out, sgn_trace_span* spans, uint64_t span_cap,
+             uint64_t* n_spans, DelayState* dl) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  const uint64_t sp_cap = std::min<uint64_t>(nH, n);  // (at most one span per host and per record)
+  const TakeLay L = take_lay(nH, sp_cap, n, n_up);
+  if (int rc = take_ensure(ctx, what, L.bytes)) return rc;
+  char* m = (char*)ctx->take_mem;
+  if (!d_src) d_src = (const sgn_trace_rec*)(m + L.up);
+  TakeHdr* d_hdr = (TakeHdr*)(m + L.hdr);
+  unsigned long long* d_cnt = (unsigned long long*)(m + L.cnt);
+  unsigned long long* d_mx = (unsigned long long*)(m + L.mx);
+  unsigned long long* d_mn = (unsigned long long*)(m + L.mn);
+  uint64_t* d_off = (uint64_t*)(m + L.off);
+  sgn_trace_span* d_spans = (sgn_trace_span*)(m + L.spans);
+  uint64_t* d_staging = (uint64_t*)(m + L.staging);
+  ReportEvents<6> E;  // (created per take and destroyed on every way out)
+  if (!E.make()) return set_error(ctx, SGN_EDEVICE, std::string("hipEventCreate failed (") + what + ")");
+  hipStream_t st = ctx->stream;
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTakeMaxBlocks, (n + kTakeRecs - 1) / kTakeRecs);
+  const std::string pre = std::string(what) + ": ";
+
+  SGN_HIP(ctx, hipMemsetAsync(m + L.hdr, 0, L.mn - L.hdr, st));  // header, cnt, mx
+  SGN_HIP(ctx, hipMemsetAsync(d_mn, 0xFF, (size_t)nH * 8, st));
+  (void)hipEventRecord(E[0], st);
+  hipLaunchKernelGGL(k_take_count, dim3(blocks), dim3(kTakeThreads), 0, st, d_src, n, lo, nH, d_cnt, d_mn, d_mx, d_hdr);
+  (void)hipEventRecord(E[1], st);
+  hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(kScanThreads), 0, st, (const unsigned long long*)d_cnt,
+                     (const unsigned long long*)d_mn, (const unsigned long long*)d_mx, lo, nH, d_off, d_spans, sp_cap, d_hdr);
+  (void)hipEventRecord(E[2], st);
+  TakeHdr h{};
+  if (int rc = read_header(ctx, d_hdr, &h)) return rc;
+  auto bad = [&](const TakeHdr& x) {
+    const char* why = x.err & TAKE_EHOST  ? "a record of a host this shard does not own: host "
+                      : x.err & TAKE_ESEQ ? "the pending records do not carry consecutive seq: host "
+                                          : "a record outside its host's span: host ";
+    return set_error(ctx, SGN_EDEVICE, pre + why + std::to_string(x.err_host) + " (nothing was taken)");
+  };
+  if (h.err) return bad(h);
+  if (h.total != n || h.n_spans > sp_cap)
+    return set_error(ctx, SGN_EDEVICE, pre + "the per-host counts add up to " + std::to_string(h.total) + " of " +
+                                           std::to_string(n) + " pending records (nothing was taken)");
+  if (!discard && (cap < n || (spans && span_cap < h.n_spans))) {
+    *n_out = n;
+    if (n_spans) *n_spans = h.n_spans;
+    return set_error(ctx, SGN_ERANGE, pre + std::to_string(n) + " records of " + std::to_string(h.n_spans) +
+                                          " hosts are pending, the caller's arrays are smaller (nothing was taken)");
+  }
+  (void)hipEventRecord(E[3], st);
+  hipLaunchKernelGGL(k_take_scatter, dim3(blocks), dim3(kTakeThreads), 0, st, d_src, n, lo, nH, (const unsigned long long*)d_cnt,
+                     (const unsigned long long*)d_mn, (const uint64_t*)d_off, d_staging, d_hdr);
+  (void)hipEventRecord(E[4], st);
+  if (int rc = read_header(ctx, d_hdr, &h)) return rc;
+  if (h.err) return bad(h);
+  if (dl) {  // the report reads the ordered records where they are; nothing it keeps changes before the commit
+    const DelayFoldIn in{d_staging, d_spans, d_cnt, d_off, n, h.n_spans, lo, nH};
+    if (int rc = delay_fold_prepare(ctx, dl, in, what)) return rc;
+  }
+  if (!discard) {
+    SGN_HIP(ctx, hipMemcpyAsync(out, d_staging, n * sizeof(sgn_trace_rec), hipMemcpyDeviceToHost, st));
+    if (spans && h.n_spans)
+      SGN_HIP(ctx, hipMemcpyAsync(spans, d_spans, h.n_spans * sizeof(sgn_trace_span), hipMemcpyDeviceToHost, st));
+  }
+  (void)hipEventRecord(E[5], st);
+  SGN_HIP(ctx, hipStreamSynchronize(st));
+  if (dl) {
+    if (int rc = delay_fold_commit(ctx, dl, n)) return rc;
+    sgn_delay_timing& D = ctx->dl_timing;
+    D.order_ms[0] = elapsed_ms(E[0], E[1]);
+    D.order_ms[1] = elapsed_ms(E[1], E[2]);
+    D.order_ms[2] = elapsed_ms(E[3], E[4]);
+    D.total_ms = ms_since(t_begin);
+  }
+  if (n_out) *n_out = n;
+  if (n_spans) *n_spans = h.n_spans;
+  sgn_trace_take_timing& T = ctx->take_timing;
+  T.kernel_ms[0] = elapsed_ms(E[0], E[1]);
+  T.kernel_ms[1] = elapsed_ms(E[1], E[2]);
+  T.kernel_ms[2] = elapsed_ms(E[3], E[4]);
+  T.copy_ms = discard ? 0.0 : elapsed_ms(E[4], E[5]);
+  T.records = n;
+  T.hosts = h.n_spans;
+  T.total_ms = ms_since(t_begin);
+  return 0;
+}
+
+int trace_take_common(sgn_ctx* ctx, const char* what, bool discard, sgn_trace_rec* out, uint64_t cap, uint64_t* n_out,
+                      sgn_trace_span* spans, uint64_t span_cap, uint64_t* n_spans) {
+  if (int rc = take_precheck(ctx, what)) return rc;
+  if (discard && !ctx->dl) return set_error(ctx, SGN_ESTATE, std::string(what) + ": the report is not enabled (sgn_delay_enable)");
+  const auto t_begin = std::chrono::steady_clock::now();
+  SGN_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = sync_ctrl(ctx)) return rc;  // (a trace overflow since the last take is reported here)
+  const DevSim& S = ctx->S;
+  const uint64_t tn = ctx->h_ctrl->trace_n;
+  const uint64_t n = tn > ctx->trace_base ? tn - ctx->trace_base : 0;
+  ctx->take_timing = sgn_trace_take_timing{};
+  if (ctx->dl)
+    if (int rc = delay_position_check(ctx, what)) return rc;
+  if (n > ctx->trace_cap) return set_error(ctx, SGN_EOVERFLOW, std::string(what) + ": more records pending than the trace buffer holds");
+  if (n == 0) {
+    if (ctx->dl) delay_position_set(ctx, ctx->trace_base, true);
+    ctx->take_timing.total_ms = ms_since(t_begin);
+    return 0;
+  }
+  if (int rc = take_run(ctx, what, (const sgn_trace_rec*)ctx->trace_buf, n, 0, S.lo, S.nH, discard, out, cap, n_out, spans, span_cap,
+                        n_spans, ctx->dl))
+    return rc;
+  // the buffer is empty: the next record goes to its start
+  if (int rc = trace_view_set(ctx, tn)) return rc;
+  if (ctx->dl) delay_position_set(ctx, tn, true);
+  ctx->take_timing.total_ms = ms_since(t_begin);
   return 0;
 }
 
@@ -252,96 +389,7 @@ int sgn_trace_take(sgn_ctx* ctx, sgn_trace_rec* out, uint64_t cap, uint64_t* n_o
   if (n_spans) *n_spans = 0;
   if (!ctx || !n_out || (!out && cap) || (!spans && span_cap))
     return ctx ? set_error(ctx, SGN_EINVAL, "sgn_trace_take: null argument") : SGN_EINVAL;
-  if (int rc = take_precheck(ctx, "sgn_trace_take")) return rc;
-  const auto t_begin = std::chrono::steady_clock::now();
-  SGN_HIP(ctx, hipSetDevice(ctx->device));
-  if (int rc = sync_ctrl(ctx)) return rc;  // (a trace overflow since the last take is reported here)
-  const DevSim& S = ctx->S;
-  const uint64_t tn = ctx->h_ctrl->trace_n;
-  const uint64_t n = tn > ctx->trace_base ? tn - ctx->trace_base : 0;
-  ctx->take_timing = sgn_trace_take_timing{};
-  if (n > ctx->trace_cap) return set_error(ctx, SGN_EOVERFLOW, "sgn_trace_take: more records pending than the trace buffer holds");
-  if (n == 0) {
-    ctx->take_timing.total_ms = ms_since(t_begin);
-    return 0;
-  }
-  const uint32_t nH = S.nH;
-  const uint64_t sp_cap = std::min<uint64_t>(nH, n);  // (at most one span per host and per record)
-  const TakeLay L = take_lay(nH, sp_cap, n);
-  if (ctx->take_bytes < L.bytes) {
-    if (ctx->take_mem) (void)hipFree(ctx->take_mem);
-    ctx->take_mem = nullptr;
-    ctx->take_bytes = 0;
-    if (hipMalloc(&ctx->take_mem, L.bytes) != hipSuccess) {
-      ctx->take_mem = nullptr;
-      return set_error(ctx, SGN_ENOMEM, "device allocation failed (sgn_trace_take)");
-    }
-    ctx->take_bytes = L.bytes;
-  }
-  char* m = (char*)ctx->take_mem;
-  TakeHdr* d_hdr = (TakeHdr*)(m + L.hdr);
-  unsigned long long* d_cnt = (unsigned long long*)(m + L.cnt);
-  unsigned long long* d_mx = (unsigned long long*)(m + L.mx);
-  unsigned long long* d_mn = (unsigned long long*)(m + L.mn);
-  uint64_t* d_off = (uint64_t*)(m + L.off);
-  sgn_trace_span* d_spans = (sgn_trace_span*)(m + L.spans);
-  uint64_t* d_staging = (uint64_t*)(m + L.staging);
-  ReportEvents<6> E;  // (created per take and destroyed on every way out)
-  if (!E.make()) return set_error(ctx, SGN_EDEVICE, "hipEventCreate failed (sgn_trace_take)");
-  hipStream_t st = ctx->stream;
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTakeMaxBlocks, (n + kTakeRecs - 1) / kTakeRecs);
-
-  SGN_HIP(ctx, hipMemsetAsync(m + L.hdr, 0, L.mn - L.hdr, st));  // header, cnt, mx
-  SGN_HIP(ctx, hipMemsetAsync(d_mn, 0xFF, (size_t)nH * 8, st));
-  (void)hipEventRecord(E[0], st);
-  hipLaunchKernelGGL(k_take_count, dim3(blocks), dim3(kTakeThreads), 0, st, (const sgn_trace_rec*)ctx->trace_buf, n, S.lo, nH,
-                     d_cnt, d_mn, d_mx, d_hdr);
-  (void)hipEventRecord(E[1], st);
-  hipLaunchKernelGGL(k_take_scan, dim3(1), dim3(kScanThreads), 0, st, (const unsigned long long*)d_cnt,
-                     (const unsigned long long*)d_mn, (const unsigned long long*)d_mx, S.lo, nH, d_off, d_spans, sp_cap, d_hdr);
-  (void)hipEventRecord(E[2], st);
-  TakeHdr h{};
-  if (int rc = read_header(ctx, d_hdr, &h)) return rc;
-  auto bad = [&](const TakeHdr& x) {
-    const char* why = x.err & TAKE_EHOST  ? "a record of a host this shard does not own: host "
-                      : x.err & TAKE_ESEQ ? "the pending records do not carry consecutive seq: host "
-                                          : "a record outside its host's span: host ";
-    return set_error(ctx, SGN_EDEVICE, std::string("sgn_trace_take: ") + why + std::to_string(x.err_host) + " (nothing was taken)");
-  };
-  if (h.err) return bad(h);
-  if (h.total != n || h.n_spans > sp_cap)
-    return set_error(ctx, SGN_EDEVICE, "sgn_trace_take: the per-host counts add up to " + std::to_string(h.total) + " of " +
-                                           std::to_string(n) + " pending records (nothing was taken)");
-  if (cap < n || (spans && span_cap < h.n_spans)) {
-    *n_out = n;
-    if (n_spans) *n_spans = h.n_spans;
-    return set_error(ctx, SGN_ERANGE, "sgn_trace_take: " + std::to_string(n) + " records of " + std::to_string(h.n_spans) +
-                                          " hosts are pending, the caller's arrays are smaller (nothing was taken)");
-  }
-  (void)hipEventRecord(E[3], st);
-  hipLaunchKernelGGL(k_take_scatter, dim3(blocks), dim3(kTakeThreads), 0, st, (const sgn_trace_rec*)ctx->trace_buf, n, S.lo, nH,
-                     (const unsigned long long*)d_cnt, (const unsigned long long*)d_mn, (const uint64_t*)d_off, d_staging, d_hdr);
-  (void)hipEventRecord(E[4], st);
-  if (int rc = read_header(ctx, d_hdr, &h)) return rc;
-  if (h.err) return bad(h);
-  SGN_HIP(ctx, hipMemcpyAsync(out, d_staging, n * sizeof(sgn_trace_rec), hipMemcpyDeviceToHost, st));
-  if (spans && h.n_spans)
-    SGN_HIP(ctx, hipMemcpyAsync(spans, d_spans, h.n_spans * sizeof(sgn_trace_span), hipMemcpyDeviceToHost, st));
-  (void)hipEventRecord(E[5], st);
-  SGN_HIP(ctx, hipStreamSynchronize(st));
-  // the buffer is empty: the next record goes to its start
-  if (int rc = trace_view_set(ctx, tn)) return rc;
-  *n_out = n;
-  if (n_spans) *n_spans = h.n_spans;
-  sgn_trace_take_timing& T = ctx->take_timing;
-  T.kernel_ms[0] = elapsed_ms(E[0], E[1]);
-  T.kernel_ms[1] = elapsed_ms(E[1], E[2]);
-  T.kernel_ms[2] = elapsed_ms(E[3], E[4]);
-  T.copy_ms = elapsed_ms(E[4], E[5]);
-  T.records = n;
-  T.hosts = h.n_spans;
-  T.total_ms = ms_since(t_begin);
-  return 0;
+  return trace_take_common(ctx, "sgn_trace_take", false, out, cap, n_out, spans, span_cap, n_spans);
 }
 
 int sgn_trace_take_timing_get(sgn_ctx* ctx, sgn_trace_take_timing* out) {

@@ -221,6 +221,42 @@ class DrainTakeTiming(C.Structure):
                 ("spans_by_class", C.c_uint64 * 3), ("wave_max", C.c_uint32), ("tile", C.c_uint32)]
 
 
+DELAY_BINS = 48
+# sgn_delay_info::total, in order
+DELAY_TOTALS = ("delivered", "dropped", "delay_sum_delivered", "delay_sum_dropped", "standing", "unmatched")
+_DELAY_ROW = [("host", "u4"), ("reserved", "u4"), ("standing", "u4"), ("unmatched", "u4"), ("delivered", "u8"), ("dropped", "u8"),
+              ("delay_sum_delivered", "u8"), ("delay_sum_dropped", "u8"), ("delay_max", "u8"), ("standing_oldest", "u8")]
+_DELAY_INFO = [("rounds", "u8"), ("window_start", "u8"), ("window_end", "u8"), ("folds", "u8"), ("records", "u8"),
+               ("hosts", "u8"), ("rows", "u8"), ("total", "u8", 6), ("delay_max", "u8"), ("delay_max_host", "u4"),
+               ("pad0", "u4"), ("hist_delivered", "u8", DELAY_BINS), ("hist_dropped", "u8", DELAY_BINS)]
+
+
+class DelayRow(C.Structure):
+    _fields_ = [(n, {"u4": C.c_uint32, "u8": C.c_uint64}[t]) for n, t in _DELAY_ROW]
+
+
+class DelayInfo(C.Structure):
+    _fields_ = [(f[0], {"u4": C.c_uint32, "u8": C.c_uint64}[f[1]] * f[2] if len(f) > 2 else {"u4": C.c_uint32, "u8": C.c_uint64}[f[1]])
+                for f in _DELAY_INFO]
+
+
+class DelayTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_double), ("order_ms", C.c_double * 3), ("kernel_ms", C.c_double * 5),
+                ("records", C.c_uint64), ("hosts", C.c_uint64), ("largest_span", C.c_uint64), ("carry_entries", C.c_uint64),
+                ("spans_by_class", C.c_uint64 * 2), ("wave_max", C.c_uint32), ("tile", C.c_uint32)]
+
+
+DELAY_ROW_DTYPE = np.dtype([(n, "<" + t) for n, t in _DELAY_ROW])
+assert DELAY_ROW_DTYPE.itemsize == C.sizeof(DelayRow) == 64
+assert C.sizeof(DelayInfo) == 120 + 16 * DELAY_BINS
+
+
+def delay_bin_edges():
+    """The upper edges of the DELAY_BINS histogram bins, in ns: bin 0 holds delay == 0 (edge 0), bin k
+    2^(k-1) <= delay < 2^k (edge 2^k - 1), the last bin everything above (edge: the largest u64)."""
+    return [0] + [(1 << k) - 1 for k in range(1, DELAY_BINS - 1)] + [EMUTIME_INVALID]
+
+
 def pkt_soa(src_host, dst_ip, payload_len, send_time, handle=None, wire_len=None):
     """(PktSoa, keep-alive arrays) for sgn_submit / ora_sim_submit."""
     a = [np.ascontiguousarray(src_host, dtype=np.uint32), np.ascontiguousarray(dst_ip, dtype=np.uint32),
@@ -419,6 +455,13 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         "sgn_sample_timing_get": (C.c_int, [vp, C.POINTER(SampleTiming)]),
         "sgn_backlog": (C.c_int, [vp, C.POINTER(BacklogRow), C.c_uint64, u64p, C.POINTER(BacklogInfo)]),
         "sgn_backlog_timing_get": (C.c_int, [vp, C.POINTER(BacklogTiming)]),
+        "sgn_delay_enable": (C.c_int, [vp]),
+        "sgn_delay_fold": (C.c_int, [vp, C.POINTER(DelayInfo)]),
+        "sgn_delay_get": (C.c_int, [vp, C.POINTER(DelayRow), C.c_uint64, u64p, C.POINTER(DelayInfo)]),
+        "sgn_delay_clear": (C.c_int, [vp]),
+        "sgn_delay_timing_get": (C.c_int, [vp, C.POINTER(DelayTiming)]),
+        "sgn_selftest_delay_fold": (C.c_int, [vp, C.POINTER(TraceRec), u64p, C.c_uint32, C.c_uint32, C.c_uint32, u32p,
+                                              C.POINTER(DelayRow), C.c_uint64, u64p, C.POINTER(DelayInfo)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -811,6 +854,51 @@ class Context:
         return {"total_ms": t.total_ms, "kernel_ms": list(t.kernel_ms), "copy_ms": t.copy_ms,
                 "hosts": t.hosts, "rows": t.rows, "calendar_runs": t.calendar_runs}
 
+    # ---- the router delay report: queueing delay per packet, folded on the device (sgn_delay_*) ----
+    def delay_enable(self):
+        """After sim_init on a traced context with no trace record pending: starts the report from
+        the state as it is now (what stands at a router becomes unknown carry entries)."""
+        self.check(self.L.sgn_delay_enable(self.h))
+
+    def delay_fold(self):
+        """A take whose records stay on the device: every pending trace record is ordered, folded
+        into the report and dropped. Returns the info as a dict (Delay.info)."""
+        info = DelayInfo()
+        self.check(self.L.sgn_delay_fold(self.h, C.byref(info)))
+        return Delay(info).info
+
+    def delay(self, rows=True, cap=None):
+        """The report since the last enable or clear, as a Delay. rows=False: the totals only. cap:
+        the row array's size (default: the row count, asked for first); too small raises SgnError
+        with rc ERANGE, .needed = the row count, .info = the info and .out = the untouched array."""
+        info = DelayInfo()
+        n = C.c_uint64()
+        if cap is None:
+            self.check(self.L.sgn_delay_get(self.h, None, 0, C.byref(n), C.byref(info)))
+            if not rows or n.value == 0:
+                return Delay(info, None)
+            cap = n.value
+        out = np.zeros(cap, dtype=DELAY_ROW_DTYPE)
+        rc = self.L.sgn_delay_get(self.h, out.ctypes.data_as(C.POINTER(DelayRow)) if cap else None, cap, C.byref(n), C.byref(info))
+        if rc != 0:
+            e = SgnError(rc, self.L.sgn_last_error(self.h).decode())
+            e.needed = n.value
+            e.info = Delay(info).info
+            e.out = out
+            raise e
+        return Delay(info, out[: n.value] if rows else None)
+
+    def delay_clear(self):
+        """Zeroes the accumulators and histograms; the carry stays (intervals: delay() + delay_clear())."""
+        self.check(self.L.sgn_delay_clear(self.h))
+
+    def delay_timing(self):
+        t = DelayTiming()
+        self.check(self.L.sgn_delay_timing_get(self.h, C.byref(t)))
+        return {"total_ms": t.total_ms, "order_ms": list(t.order_ms), "kernel_ms": list(t.kernel_ms), "records": t.records,
+                "hosts": t.hosts, "largest_span": t.largest_span, "carry_entries": t.carry_entries,
+                "spans_by_class": list(t.spans_by_class), "wave_max": t.wave_max, "tile": t.tile}
+
     # ---- CPU-resident applications (TRAFFIC_EXTERNAL) and the host RNG ----
     def drain_enable(self, cap):
         self.check(self.L.sgn_drain_enable(self.h, cap))
@@ -972,6 +1060,29 @@ def selftest_drain_order(ctx, recs, host_lo, n_hosts, span_cap=None):
         e.out, e.needed = out, ns.value
         raise e
     return out, spans[: ns.value]
+
+
+def selftest_delay_fold(ctx, recs, piece_ends, host_lo, n_hosts, standing0=None, cap=None):
+    """The delay report's kernels on the caller's trace records (TRACE_DTYPE) of hosts [host_lo,
+    host_lo + n_hosts), cut into the consecutive pieces recs[piece_ends[i - 1] : piece_ends[i]] (any
+    order inside a piece), the carry starting from standing0 unknown entries per host. Returns the
+    final Delay. Needs no simulation. An error (SgnError) carries .needed, the row count."""
+    recs = np.ascontiguousarray(recs, dtype=TRACE_DTYPE)
+    ends = np.ascontiguousarray(piece_ends, dtype=np.uint64)
+    s0 = None if standing0 is None else np.ascontiguousarray(standing0, dtype=np.uint32)
+    cap = n_hosts if cap is None else cap
+    rows = np.zeros(cap, dtype=DELAY_ROW_DTYPE)
+    info = DelayInfo()
+    n = C.c_uint64()
+    rc = ctx.L.sgn_selftest_delay_fold(ctx.h, recs.ctypes.data_as(C.POINTER(TraceRec)) if len(recs) else None,
+                                       ptr(ends, C.c_uint64) if len(ends) else None, len(ends), host_lo, n_hosts,
+                                       ptr(s0, C.c_uint32) if s0 is not None and len(s0) else None,
+                                       rows.ctypes.data_as(C.POINTER(DelayRow)) if cap else None, cap, C.byref(n), C.byref(info))
+    if rc != 0:
+        e = SgnError(rc, ctx.L.sgn_last_error(ctx.h).decode())
+        e.needed = n.value
+        raise e
+    return Delay(info, rows[: n.value])
 
 
 def shards_run_until(shards, t_emulated):
@@ -1269,6 +1380,51 @@ class Backlog:
             v[v == EMUTIME_INVALID] = 0
         out[self.rows["host"]] = v
         return out
+
+
+class Delay:
+    """One router delay report (Context.delay): .info, a dict of sgn_delay_info (total: the six sums in
+    DELAY_TOTALS order; .totals: the same by name; hist_delivered / hist_dropped: DELAY_BINS counts),
+    and .rows (DELAY_ROW_DTYPE, ascending by host; empty for the totals-only form)."""
+
+    def __init__(self, info, rows=None):
+        self.info = {f[0]: ([int(v) for v in getattr(info, f[0])] if len(f) > 2 else int(getattr(info, f[0])))
+                     for f in _DELAY_INFO if not f[0].startswith("pad")}
+        self.rows = np.zeros(0, DELAY_ROW_DTYPE) if rows is None else np.ascontiguousarray(rows, dtype=DELAY_ROW_DTYPE)
+
+    @property
+    def totals(self):
+        return dict(zip(DELAY_TOTALS, self.info["total"]))
+
+    def quantile(self, q, dropped=False):
+        """The upper edge, in ns, of the histogram bin that holds the q-th (0 < q <= 1) matched packet
+        in delay order: delivered packets, or CoDel-dropped ones. None when no packet was matched."""
+        hist = self.info["hist_dropped" if dropped else "hist_delivered"]
+        n = sum(hist)
+        if n == 0:
+            return None
+        want = min(n, max(1, int(np.ceil(q * n))))  # (at least the first packet)
+        seen = 0
+        for edge, c in zip(delay_bin_edges(), hist):
+            seen += c
+            if seen >= want:
+                return edge
+        return delay_bin_edges()[-1]
+
+
+def run_delays(ctx, step_ns, until=None):
+    """Runs ctx (a traced Context with delay_enable() done) to its end, or until the next window would
+    start at or after `until`, in steps of step_ns of simulated time: run_until, then delay_fold. The
+    trace buffer need only hold what one step produces. Returns the final Delay."""
+    while True:
+        ws, _, active = ctx.window()
+        if not active or (until is not None and ws >= until):
+            break
+        t = ws + step_ns
+        ctx.run_until(t if until is None else min(t, until))
+        ctx.delay_fold()
+    ctx.delay_fold()  # (records produced before the call, if any)
+    return ctx.delay()
 
 
 def run_sampled(ctx_or_shards, interval_ns, until=None, backlog=False):
